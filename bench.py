@@ -717,6 +717,47 @@ def ppnet_leg(torch, dev, pb, mb, batch, steps, world, rank, cpu_leg, hold=None)
     return out
 
 
+DUMP_SAMPLE_MAPS = 64           # maps whose full grid / path points --dump-outputs writes (the whole step's grids are 655 MB)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(torch, out_dir, pb, mb):
+    """--dump-outputs: what the caller of the timed path receives from its last step, as DIR/<name>.npy (float64; the grids
+    float32) — stage A's PathsBatch (paths_*) and stage B's MapsBatch (maps_*).  Rows past a count (obstacles, hull) are zeroed:
+    the buffers are reused and keep earlier steps' values there.  grid and pathpoint are kept for DUMP_SAMPLE_MAPS maps, rows
+    sorted(np.random.default_rng(0).choice(n, DUMP_SAMPLE_MAPS, replace=False)) of the step.  Returns the bytes written."""
+    import numpy as np
+
+    def upto(t, n):
+        live = torch.arange(t.shape[1], device=t.device)[None, :] < n.reshape(-1, 1)
+        return t * live.reshape(live.shape + (1,) * (t.dim() - 2)).to(t.dtype)
+
+    rows = torch.from_numpy(np.sort(np.random.default_rng(0).choice(mb.n, DUMP_SAMPLE_MAPS, replace=False))).to(mb.device)
+    arrays = {}
+    for name, _ in type(pb.struct)._fields_:
+        t = getattr(pb, name)
+        if t is not None:
+            arrays["paths_" + name] = t
+    arrays["paths_obstacles"] = upto(pb.obstacles, pb.n_obstacles)
+    arrays["paths_hull"] = upto(pb.hull, pb.hull_n)
+    for name, _ in type(mb.struct)._fields_:
+        t = getattr(mb, name)
+        if t is not None and name not in ("grid", "pathpoint"):
+            arrays["maps_" + name] = t
+    arrays["maps_obstacles"] = upto(mb.obstacles, mb.n_obstacles[:, 0])
+    arrays["maps_grid_sample"] = mb.grid.index_select(0, rows).float()
+    if mb.pathpoint is not None:
+        arrays["maps_pathpoint_sample"] = mb.pathpoint.index_select(0, rows)
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return total
+
+
 def pick_path_group(warmup, steps):
     """Steps served by one stage-A launch (BENCH_PATH_GROUP overrides).  Every cross-stream hand-off is a marker packet the
     compute queue drains before the next kernel starts (~5 us on this runtime): with one stage-A launch, one wait and one
@@ -755,6 +796,8 @@ def main():
     ap.add_argument("--segnet", choices=["dinat_setr", "nat_uper", "both"], default="both",
                     help="SegNet legs: dinat_setr = BASELINE config 3 (DiNAT-B + SETR-UP, inside the ppnet object); nat_uper = the reference's "
                          "default config (NAT-Base + UPerHead) as a leg of its own; both (default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (stage A's paths, stage B's maps; rank 0's) to DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -826,11 +869,14 @@ def main():
     launched = [-1]               # newest batch whose stage A has been launched
     stage_a_evs = []              # (start, end) events around the sampled stage-A launches of the timed region, on their own streams
     stage_a_on = [False]
+    id_shift = [0]                # steps subtracted from a step's index to give its batch id (set after the clock-warm phase)
+    last_out = [None]             # (paths, maps) of the newest step
 
     def launch_paths(it):
         """Stage A of path group `it` (the paths of steps it*GROUP .. it*GROUP + GROUP - 1)."""
         b = it % NPB
         sp = s_paths[it % DEPTH]
+        bid = it - id_shift[0] // GROUP
         with torch.cuda.stream(sp):
             if consumed[b] is not None:
                 sp.wait_event(consumed[b])
@@ -839,13 +885,13 @@ def main():
                 ea = torch.cuda.Event(enable_timing=True)
                 ea.record(sp)
             if GROUP == 1:
-                first_path, _, _ = shard.local_ids(PATHS * world, PLACEMENTS, rank, world, batch_index=it)
+                first_path, _, _ = shard.local_ids(PATHS * world, PLACEMENTS, rank, world, batch_index=bid)
                 edage.generate_paths(PATHS, R, MAP_SIZE, CLEARANCE, seed=SEED, first_path_id=first_path, device=dev, out=pbs[b])
             else:
                 # path ids of this rank for GROUP consecutive batches are not contiguous across ranks: one launch per batch id
                 # range would defeat the grouping, so a group draws the ids [first(it*GROUP) .. ) of a world whose batch is
                 # GROUP times as large — same streams for any N, every id used once
-                first_path, _, _ = shard.local_ids(PATHS * GROUP * world, PLACEMENTS, rank, world, batch_index=it)
+                first_path, _, _ = shard.local_ids(PATHS * GROUP * world, PLACEMENTS, rank, world, batch_index=bid)
                 edage.generate_paths(PATHS * GROUP, R, MAP_SIZE, CLEARANCE, seed=SEED, first_path_id=first_path, device=dev, out=pbs[b])
             ready[b] = torch.cuda.Event(enable_timing=ea is not None)
             ready[b].record(sp)
@@ -858,9 +904,9 @@ def main():
         grp, sub = divmod(it, GROUP)
         b = grp % NPB
         if GROUP == 1:
-            _, _, first_map = shard.local_ids(PATHS * world, PLACEMENTS, rank, world, batch_index=it)
+            _, _, first_map = shard.local_ids(PATHS * world, PLACEMENTS, rank, world, batch_index=it - id_shift[0])
         else:
-            fp, _, _ = shard.local_ids(PATHS * GROUP * world, PLACEMENTS, rank, world, batch_index=grp)
+            fp, _, _ = shard.local_ids(PATHS * GROUP * world, PLACEMENTS, rank, world, batch_index=grp - id_shift[0] // GROUP)
             first_map = (fp + sub * PATHS) * PLACEMENTS
         if sub == 0:
             while launched[0] < grp + DEPTH - 1:
@@ -881,6 +927,7 @@ def main():
             ring.begin_step()                 # before a group's first step: the slot's previous collective has read it
             target = mviews[ring.slot][ring.k]
         edage.generate_maps(pviews[b][sub], PLACEMENTS, OBST_SIZE, K, seed=SEED, first_map_id=first_map, out=target)
+        last_out[0] = (pviews[b][sub], target)
         ev1 = None
         if sub == GROUP - 1:
             ev1 = torch.cuda.Event(enable_timing=sampled)      # a timestamp only on the sampled groups
@@ -912,6 +959,12 @@ def main():
         torch.cuda.synchronize()
     clock_warm_ms = (time.perf_counter() - tw) * 1e3
     first = args.warmup + warm_steps
+    # The clock-warm phase runs for a wall time, so its step count differs from run to run.  The timed steps take the batch ids
+    # that follow --warmup instead (same arguments, same instances in every run); the stage-A groups already launched ahead
+    # for them are launched again under those ids, outside the clock.
+    id_shift[0] = warm_steps
+    for g in range(first // GROUP, launched[0] + 1):
+        launch_paths(g)
     if exchange:
         ring.flush()                          # the warm steps' partial group leaves outside the clock
         gathers_before = ring.n_gathers
@@ -941,6 +994,9 @@ def main():
     placed = float(((mb.flags & 2) == 0).double().mean().item())
     total_instances = world * n_local * args.steps
     value = total_instances / elapsed
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(torch, args.dump_outputs, *last_out[0])
 
     ppnet = None
     if not args.no_ppnet:
@@ -989,6 +1045,8 @@ def main():
             "placement_success": round(placed, 4),
             "mean_obstacles_per_map": round(k_tot, 2),
         }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
         if shared_gpu:
             out["rehearsal"] = ("BENCH_REHEARSE_SHARED_GPU: every rank on one GPU, gloo group, gathered rows through the host - the N > 1 control "
                                 "flow run for its own sake, not a measurement")

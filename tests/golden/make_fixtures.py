@@ -19,6 +19,7 @@ stubs make them meaningless (torchvision / libjpeg rasters are "parity unpinned"
 Nothing from the reference is copied: fixtures hold numbers only.
 
     python tests/golden/make_fixtures.py        # rewrites tests/golden/*.npz
+    python tests/golden/make_fixtures.py torch_resample     # g17 alone (PyTorch only, no reference modules)
 """
 import io
 import json
@@ -641,8 +642,41 @@ def fixture_nat_wiring():
     sys.path.remove(seg)
 
 
+# ----------------------------------------------------------------------------- G17: PyTorch's resample rasters
+def fixture_torch_resample():
+    """PyTorch's results for the resample tests on random images of tests/test_oracle_golden.py (its cases, and its _tv_*
+    helpers: the composition of torch ops torchvision 0.12 makes), recorded as the pixels where they differ from the same
+    composition in float64 (its _f64_* helpers).  The float32 rounding of PyTorch-CPU's bmm follows the code path MKL's sgemm
+    takes on the CPU: record on an Intel CPU with AVX-512, whose path the oracle and the HIP kernels follow."""
+    with open("/proc/cpuinfo") as f:
+        intel = "GenuineIntel" in f.read()
+    assert intel and torch.backends.mkl.is_available() and torch.backends.cpu.get_cpu_capability() == "AVX512"
+    root = os.path.dirname(os.path.dirname(OUT))
+    sys.path[:0] = [root, os.path.join(root, "tests")]
+    import test_oracle_golden as T
+    out = {}
+
+    def record(key, torch_result, f64_result):
+        at = np.flatnonzero(torch_result != f64_result)
+        out[key + "/at"], out[key + "/val"] = at, torch_result.reshape(-1)[at]
+
+    for R in (64, 224, 256):
+        for key, img, angle, t in T._placement_cases(R):
+            record(key, T._tv_translate(T._tv_random_rotation(img, -angle), t[0], t[1]) > 0.5,
+                   T._f64_translate(T._f64_rotate(img, float(np.float32(-angle))), t[0], t[1]) > 0.5)
+    for key, a, img in T._rotation_cases():
+        record(key, T._tv_random_rotation(img, a) > 0.5, T._f64_rotate(img, float(np.float32(a))) > 0.5)
+    for key, h, w, m in T._affine_cases():
+        idx = np.arange(1, h * w + 1, dtype=np.float32).reshape(h, w)
+        record(key, T._tv_grid_sample(idx, m), T._f64_grid_sample(idx, m))
+    np.savez_compressed(os.path.join(OUT, "g17_torch_resample.npz"), **out)
+
+
 def main():
     _install_stubs()
+    if len(sys.argv) > 1 and sys.argv[1] == "torch_resample":
+        fixture_torch_resample()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "nat_wiring":
         fixture_nat_wiring()
         return
@@ -680,6 +714,7 @@ def main():
         sys.modules.pop(mod, None)
     fixture_aevit()
     fixture_nat_wiring()
+    fixture_torch_resample()
     for f in sorted(os.listdir(OUT)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(OUT, f)))

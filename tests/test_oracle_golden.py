@@ -285,6 +285,61 @@ def _tv_translate(img, tx, ty):        # functional.affine(angle=0, translate=[t
     return _tv_grid_sample(img, E.inverse_affine_matrix(0.0, [tx, ty]))
 
 
+# PyTorch's float32 arithmetic in that composition is not the same on every host: the bmm is MKL's sgemm, whose code path
+# follows the CPU, and the oracle (the HIP kernels with it) follows the AVX-512 path.  The tests on random images below therefore
+# compare with PyTorch's results recorded on such a host (tests/golden/g17_torch_resample.npz, tests/golden/make_fixtures.py),
+# stored as the pixels where they differ from the same composition evaluated in float64 (a few per million).
+def _f64_grid_sample(img, matrix):
+    """_tv_grid_sample's composition in float64 NumPy: every operation exactly rounded, so the same result on every host
+    (grid_sample's nearest mode rounds half to even, as np.rint)."""
+    h, w = img.shape
+    th = np.asarray(matrix, dtype=np.float64).reshape(2, 3)
+    x = np.arange(w, dtype=np.float64)[None, :] + (0.5 - w * 0.5)
+    y = np.arange(h, dtype=np.float64)[:, None] + (0.5 - h * 0.5)
+    jj, ii = (np.rint(((x * th[k, 0] + y * th[k, 1] + th[k, 2]) / (0.5 * size) + 1.0) * (size / 2) - 0.5).astype(np.int64)
+              for k, size in ((0, w), (1, h)))
+    return E._gather(np.asarray(img, dtype=np.float32), ii, jj, h, w)
+
+
+def _f64_rotate(img, angle):
+    return _f64_grid_sample(img, E.inverse_affine_matrix(-angle, [0.0, 0.0]))
+
+
+def _f64_translate(img, tx, ty):
+    return _f64_grid_sample(img, E.inverse_affine_matrix(0.0, [tx, ty]))
+
+
+def _recorded(g17, key, base):
+    """PyTorch's result of case `key` as g17 records it: `base`, the float64 evaluation, with PyTorch's values where they differ."""
+    out = np.array(base)
+    out.reshape(-1)[g17[key + "/at"]] = g17[key + "/val"]
+    return out
+
+
+def _placement_cases(R):
+    rng = np.random.default_rng(R)
+    for i in range(100 if R == 64 else 34):
+        img = rng.random([R, R]) < 0.5
+        angle = rng.uniform(-180.0, 180.0)                                  # MapGenerate.py:63
+        t = [int(rng.random() ** 2 * R - R / 2), int(rng.random() ** 2 * R - R / 2)]
+        yield f"placements_R{R}/{i}", img, angle, t
+
+
+def _rotation_cases():
+    rng = np.random.default_rng(11)
+    for i in range(40):
+        a = rng.uniform(-180.0, 180.0)
+        yield f"rotation/{i}", a, rng.random([512, 512]) < 0.5
+
+
+def _affine_cases():
+    rng = np.random.default_rng(7)
+    for (h, w) in ((128, 128), (224, 224), (100, 300), (330, 444), (512, 512)):
+        for i in range(4):
+            m = E.inverse_affine_matrix(rng.uniform(-180, 180), [rng.uniform(-w / 2, w / 2), rng.uniform(-h / 2, h / 2)])
+            yield f"affine_{h}x{w}/{i}", h, w, m
+
+
 def test_inverse_affine_matrix_closed_forms():
     m = E.inverse_affine_matrix(30.0, [0.0, 0.0])
     c, s = math.cos(math.radians(30.0)), math.sin(math.radians(30.0))
@@ -311,50 +366,45 @@ def test_resample_rule_is_torchvisions_tensor_path_on_goldens(golden_dir):
 
 
 @pytest.mark.parametrize("R", [64, 224, 256])
-def test_resample_rule_is_torchvisions_tensor_path_on_placements(R):
+def test_resample_rule_is_torchvisions_tensor_path_on_placements(golden_dir, R):
     """MapGenerate.py:102-106 on 100 random placements; dense random images, so every pixel of the map is a witness
     (the float64 form of the same map differs from the primitive on ~5 pixels per million of such images)."""
-    rng = np.random.default_rng(R)
-    for _ in range(100 if R == 64 else 34):
-        img = rng.random([R, R]) < 0.5
-        angle = rng.uniform(-180.0, 180.0)                                  # MapGenerate.py:63
-        t = [int(rng.random() ** 2 * R - R / 2), int(rng.random() ** 2 * R - R / 2)]
-        want = _tv_translate(_tv_random_rotation(img, -angle), t[0], t[1]) > 0.5
+    g17 = _load(golden_dir, "g17_torch_resample.npz")
+    for key, img, angle, t in _placement_cases(R):
+        # RandomRotation's angle is float32(-angle) (test_rotation_angle_passes_through_float32)
+        want = _recorded(g17, key, _f64_translate(_f64_rotate(img, float(np.float32(-angle))), t[0], t[1]) > 0.5)
         got = E.translate_nearest(E.rotate_nearest(img, -angle), float(t[0]), float(t[1]), R, R)
         assert np.array_equal(got, want)
 
 
-def test_rotation_angle_passes_through_float32():
+def test_rotation_angle_passes_through_float32(golden_dir):
     """RandomRotation hands F.rotate the angle as a float32 value; rounds 1-4 built the matrix from the float64
     angle (oracle and kernels alike, so no HIP-vs-oracle test could see it).  The draw is float32(a) exactly, the oracle's
     rotate_nearest follows it, and on dense images the two angles give different rasters often enough to tell them apart."""
-    rng = np.random.default_rng(11)
+    g17 = _load(golden_dir, "g17_torch_resample.npz")
     differ = 0
-    for _ in range(40):
-        a = rng.uniform(-180.0, 180.0)
+    for key, a, img in _rotation_cases():
         drawn = float(torch.empty(1).uniform_(a, a).item())
         assert drawn == float(np.float32(a))
-        img = rng.random([512, 512]) < 0.5
-        want = _tv_random_rotation(img, a) > 0.5
+        want = _recorded(g17, key, _f64_rotate(img, drawn) > 0.5)
         assert np.array_equal(E.rotate_nearest(img, a), want)
-        differ += int(not np.array_equal(_tv_rotate(img, a) > 0.5, want))
+        f64_angle = E._gather(img, *E.affine_source_index(512, 512, E.inverse_affine_matrix(-a, [0.0, 0.0])), 512, 512)
+        differ += int(not np.array_equal(f64_angle, want))
     assert differ > 0          # the float64-angle form is a different raster on some of them: the test has teeth
 
 
-def test_affine_source_index_equals_grid_sample():
+def test_affine_source_index_equals_grid_sample(golden_dir):
     """The source index of every output pixel (an index image makes grid_sample return it), for matrices with rotation
     AND fractional translation, non-square and non-power-of-two sizes: pins the operation order of the float32 grid
     (k-ordered FMA chain of the sgemm) and of the unnormalisation."""
-    rng = np.random.default_rng(7)
-    for (h, w) in ((128, 128), (224, 224), (100, 300), (330, 444), (512, 512)):
-        for _ in range(4):
-            m = E.inverse_affine_matrix(rng.uniform(-180, 180), [rng.uniform(-w / 2, w / 2), rng.uniform(-h / 2, h / 2)])
-            idx = np.arange(1, h * w + 1, dtype=np.float32).reshape(h, w)
-            want = _tv_grid_sample(idx, m).astype(np.int64) - 1          # -1: zero fill
-            ii, jj = E.affine_source_index(h, w, m)
-            ok = (ii >= 0) & (ii < h) & (jj >= 0) & (jj < w)
-            got = np.where(ok, ii * w + jj, -1)
-            assert np.array_equal(got, want)
+    g17 = _load(golden_dir, "g17_torch_resample.npz")
+    for key, h, w, m in _affine_cases():
+        idx = np.arange(1, h * w + 1, dtype=np.float32).reshape(h, w)
+        want = _recorded(g17, key, _f64_grid_sample(idx, m)).astype(np.int64) - 1          # -1: zero fill
+        ii, jj = E.affine_source_index(h, w, m)
+        ok = (ii >= 0) & (ii < h) & (jj >= 0) & (jj < w)
+        got = np.where(ok, ii * w + jj, -1)
+        assert np.array_equal(got, want)
 
 
 def test_disc_raster_rule():
