@@ -65,8 +65,8 @@ extern "C" {
  * before its first real call (ppnet_amd/_lib.py does, INTEGRATION.md shows the check) — argument lists are plain pointers and
  * sizes, so a caller built against another header would link and pass, say, a batch size where a workspace pointer is expected.
  * Bumped whenever an entry point's argument list changes or an entry point is removed: 100 = rounds 1-3; 101 = round 4
- * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5. */
-#define PPN_ABI_VERSION 105
+ * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5; 106 = ppn_swin_wmsa_fwd. */
+#define PPN_ABI_VERSION 106
 int         ppn_version(void);
 const char* ppn_error_string(int code);
 int         ppn_last_hip_error(void);   /* hipError_t of the most recent PPN_E_HIP on this thread */
@@ -267,6 +267,21 @@ int ppn_na2d_fwd_padded(const void* qkv, const float* rpb, void* out, int32_t B,
  * projection and the reads of the 1.7-3x larger padded grid on DiNAT's dilated layers. */
 int ppn_na2d_fwd_vpad(const void* qkv, const void* pad_kv, const float* rpb, void* out, int32_t B, int32_t H, int32_t W,
                       int32_t Hr, int32_t Wr, int32_t heads, int32_t dilation, float scale, int32_t dtype, void* stream);
+
+/* Swin's window / shifted-window multi-head self-attention, forward (replaces the body of mmseg's ShiftWindowMSA.forward and
+ * WindowMSA.forward between the qkv and the proj Linear, SegNet/mmseg/backbones/swin.py:80-118,179-253: pad, roll, window
+ * partition, q k^T + relative position bias (+ region mask), softmax, . v, window reverse, reverse roll, crop).
+ * qkv [B][H][W][3][heads][32], real tokens only; pad_kv [3][heads][32] the k / v of every padded position (the qkv bias in the
+ * activation dtype, zeros without one: mmseg pads before the projection); rpb [heads][13][13] float32 = mmseg's
+ * relative_position_bias_table [169][heads] transposed, indexed [h][dy + 6][dx + 6] with (dy, dx) = query minus key inside the
+ * window; out [B][H][W][heads*32], only real tokens written.  The grid is padded to Hp = ceil(H/7)*7, Wp likewise (also when
+ * H or W < 7); window (wy, wx) slot (i, j) holds padded position ((7 wy + i + shift) mod Hp, (7 wx + j + shift) mod Wp).  With
+ * shift > 0, slots of different regions (per axis of the shifted frame: y < Hp-7, Hp-7 <= y < Hp-shift, the rest) get -100
+ * added to the logit (not -inf).  Logit = (q * scale) . k + bias.  window must be 7 and shift 0 or 3 (else
+ * PPN_E_UNSUPPORTED); buffers 16-byte aligned, B * windows < 2^31, heads <= 65535 (else PPN_E_INVALID, no launch).
+ * dtype 0 = float32, 1 = bfloat16 (float32 accumulation, matrix cores). */
+int ppn_swin_wmsa_fwd(const void* qkv, const void* pad_kv, const float* rpb, void* out, int32_t B, int32_t H, int32_t W,
+                      int32_t heads, int32_t window, int32_t shift, float scale, int32_t dtype, void* stream);
 
 /* Backward of ppn_na2d_fwd (the gradient NATTEN's natten2dqkrpb / natten2dav backward kernels compute; first brick of the
  * training step, GenNet/train.py:93-147, SegNet/mmseg/apis/train.py:67-167).  qkv [B][H][W][3][heads][32] and rpb as in the

@@ -361,6 +361,20 @@ int ppn_na2d_fwd_vpad(const void* qkv, const void* pad_kv, const float* rpb, voi
     return na2d_checked(qkv, pad_kv, rpb, out, B, H, W, Hr, Wr, heads, dilation, scale, dtype, stream);
 }
 
+int ppn_swin_wmsa_fwd(const void* qkv, const void* pad_kv, const float* rpb, void* out, int32_t B, int32_t H, int32_t W, int32_t heads,
+                      int32_t window, int32_t shift, float scale, int32_t dtype, void* stream) {
+    if (!qkv || !pad_kv || !rpb || !out || B <= 0 || H <= 0 || W <= 0 || heads <= 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;
+    if (window <= 0 || shift < 0 || shift >= window || !(scale > 0.0f) || scale > 3.0e38f) return PPN_E_INVALID;
+    if (window != 7 || (shift != 0 && shift != 3)) return PPN_E_UNSUPPORTED;             // Swin-B's window; shift = window // 2
+    if ((((uintptr_t)qkv | (uintptr_t)pad_kv | (uintptr_t)out) & 15) != 0) return PPN_E_INVALID;   // 16-byte loads / stores
+    if (heads > 65535) return PPN_E_INVALID;
+    const long long windows = (long long)B * ((H + 6) / 7) * ((W + 6) / 7);
+    if (windows >= 0x7fffffffLL || (long long)H * W >= 0x7fffffffLL) return PPN_E_INVALID;    // window numbers are 32-bit (token offsets 64-bit)
+    const int e = ppn::swin_wmsa_launch(qkv, pad_kv, rpb, out, B, H, W, heads, shift, scale, dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_residual_layernorm(const void* x, const void* a, const void* gamma, const void* w, const void* b, void* x_out,
                            void* y_out, int64_t rows, int32_t C, float eps, int32_t dtype, void* stream) {
     return ppn_residual_layernorm_padded(x, a, gamma, w, b, x_out, y_out, rows, C, eps, dtype, 0, 0, 0, 0, stream);

@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 from . import fused
 from .na import NeighborhoodAttention2D
+from .swin import SwinTransformer
 
 
 def drop_path(x, rate, training):
@@ -717,6 +718,41 @@ DINAT_BASE = dict(   # SegNet/configs/dinat/dinat_base.py:5-24 over _base_/model
                   dilations=[[1, 16, 1], [1, 4, 1, 8], [1, 2, 1, 3, 1, 4, 1, 2, 1, 3, 1, 4, 1, 2, 1, 3, 1, 4], [1, 2, 1, 2, 1]]),
     decode_head=dict(in_channels=1024, channels=512, num_convs=4, up_scale=2, num_classes=2, kernel_size=3))
 
+# Swin-B: SegNet/configs/_base_/models/swin.py:1-57 merged with configs/swin/swin_base.py:5-37 (SETR-UP) and
+# configs/swin/upernet_swin_base.py:5-38 (UPerHead + FCN auxiliary head).  `pretrained` (an ImageNet checkpoint path on the
+# authors' machine, swin_base.py:14) is left out: load a checkpoint with SwinTransformer.init_weights or load_state_dict.
+_SWIN_BASE_BACKBONE = dict(   # _base_/models/swin.py:7-32 with swin_base.py:7-15
+    type="SwinTransformer", pretrain_img_size=224, in_channels=3, embed_dims=128, patch_size=4, window_size=7, mlp_ratio=4,
+    depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32), strides=(4, 2, 2, 2), out_indices=(0, 1, 2, 3), qkv_bias=True, qk_scale=None,
+    patch_norm=True, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.3, use_abs_pos_embed=False, act_cfg=dict(type="GELU"),
+    norm_cfg=dict(type="LN"), with_cp=False, frozen_stages=-1, init_cfg=None)
+_SWIN_NORM_CFG = dict(type="SyncBN", requires_grad=True)
+
+SWIN_BASE_SETRUP = dict(
+    type="EncoderDecoder", pretrained=None, backbone=dict(_SWIN_BASE_BACKBONE),
+    decode_head=dict(   # swin_base.py:16-35
+        type="SETRUPHead", norm_layer=dict(type="LN", eps=1e-6, requires_grad=True), num_convs=4, up_scale=2, kernel_size=3,
+        init_cfg=[dict(type="Constant", val=1.0, bias=0, layer="LayerNorm"), dict(type="Normal", std=0.01, override=dict(name="conv_seg"))],
+        in_channels=1024, channels=512, in_index=-1, num_classes=2, norm_cfg=_SWIN_NORM_CFG, align_corners=False,
+        loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0)),
+    # _base_/models/swin.py:33-45 as swin_base.py leaves it: in_channels 256 and 19 classes, although level 2 of Swin-B has 512
+    # channels — kept as the reference merges it (the auxiliary head only runs in training, which this config cannot do as written)
+    auxiliary_head=dict(type="FCNHead", in_channels=256, in_index=2, channels=256, num_convs=1, concat_input=False, dropout_ratio=0.1,
+                        num_classes=19, norm_cfg=_SWIN_NORM_CFG, align_corners=False,
+                        loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=0.4)),
+    train_cfg=dict(), test_cfg=dict(mode="whole"))
+
+SWIN_BASE_UPER = dict(
+    type="EncoderDecoder", pretrained=None, backbone=dict(_SWIN_BASE_BACKBONE),
+    decode_head=dict(   # upernet_swin_base.py:17-29
+        type="UPerHead", in_channels=[128, 256, 512, 1024], in_index=[0, 1, 2, 3], pool_scales=(1, 2, 3, 6), channels=512,
+        dropout_ratio=0.1, num_classes=2, norm_cfg=_SWIN_NORM_CFG, align_corners=False,
+        loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0)),
+    auxiliary_head=dict(   # _base_/models/swin.py:33-45 with upernet_swin_base.py:30-33
+        type="FCNHead", in_channels=512, in_index=2, channels=256, num_convs=1, concat_input=False, dropout_ratio=0.1, num_classes=2,
+        norm_cfg=_SWIN_NORM_CFG, align_corners=False, loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=0.4)),
+    train_cfg=dict(), test_cfg=dict(mode="whole"))
+
 IMG_MEAN = (123.675, 116.28, 103.53)       # _base_/datasets/planning_seg.py:12-13
 IMG_STD = (58.395, 57.12, 57.375)
 
@@ -733,7 +769,7 @@ class SegNet(nn.Module):
         bb_type = bb_cfg.pop("type", "DiNAT")
         if pretrained is not None and bb_cfg.get("pretrained") is None:
             bb_cfg["pretrained"] = pretrained                                  # encoder_decoder.py:32-36
-        self.backbone = {"NAT": NAT, "DiNAT": DiNAT}[bb_type](**bb_cfg)
+        self.backbone = {"NAT": NAT, "DiNAT": DiNAT, "SwinTransformer": SwinTransformer}[bb_type](**bb_cfg)
         head_cfg = dict(decode_head or DINAT_BASE["decode_head"])
         head_type = head_cfg.pop("type", "SETRUPHead")
         self.decode_head = {"SETRUPHead": SETRUPHead, "UPerHead": UPerHead, "FCNHead": FCNHead}[head_type](**head_cfg)
