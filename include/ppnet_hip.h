@@ -486,8 +486,8 @@ int ppn_gemm_bf16(const void* a, const void* w, const float* bias, void* c, int6
 int32_t ppn_nat_gemm_partials(int32_t C);
 
 /* The dense half of a NAT layer at C = 256 / 512 / 1024 with everything between two projections in the GEMMs' epilogues
- * (SegNet/nat.py:62-85 `Mlp.forward`, :140-153 `NATLayer.forward`; csrc/nat_gemm.hip).  a [M][K], w [N][K] (torch Linear
- * layout), c [M][N], all bfloat16; M, N % 256 == 0, K % 64 == 0.
+ * (SegNet/nat.py:62-85 `Mlp.forward`, :140-153 `NATLayer.forward`; csrc/mfma_gemm.h, csrc/mfma_gemm.hip).  a [M][K], w [N][K]
+ * (torch Linear layout), c [M][N], all bfloat16; M, N % 256 == 0, K % 64 == 0, K >= 128.
  *   mode 0: c = LN(a) w0^T + b0 computed from the RAW rows of a: the caller passes w = w0 diag(gamma), bias = b0 + w0 beta,
  *           colsum[n] = sum_k w[n][k] (of the bfloat16 values), and stats_in [partials_in][M][2] = partial (sum, sum of squares) of
  *           every row of a (1 <= partials_in <= 4, summed in order; the LayerNorm is over the K features, eps as given):
@@ -495,13 +495,12 @@ int32_t ppn_nat_gemm_partials(int32_t C);
  *   mode 1: c = gelu(mode 0) (erf form; evaluated through a logistic fit of erf, |error| < 3e-5).
  *   mode 2: c += a w^T + bias IN PLACE, and stats_out [P][M][2], P = ppn_nat_gemm_partials(N), receives per column tile (sum, sum of
  *           squares) of every row of the NEW c over the tile's columns — of the bfloat16 values stored: what mode 0 / 1 of the
- *           next projection reads as stats_in with partials_in = P.  colsum / stats_in unused.
+ *           next projection reads as stats_in with partials_in = P.  colsum / stats_in unused.  K >= 128.
  *   The partials of a row are summed in a fixed tree (lane quarter q takes partial q), not in index order: bit-reproducible, and
  *   equal to any other order to float32 rounding.
- * Behind it since round 5 (K >= 128): ONE kernel, the persistent 256 x 256 core of csrc/mfma_gemm.h with these three epilogues (mode 2
- * reads the old c in its epilogue).  Rounds 3-4's kernels (csrc/nat_gemm.hip: the old c through the matrix pipe against an identity;
- * csrc/nat_gemm128.hip: 128 x 128 tiles) serve K = 64 and the A/B knobs PPNET_NAT_LN=old / PPNET_NAT_ACC=old.  Bit-reproducible (no
- * atomics). */
+ * Behind it: ONE kernel, the persistent 256 x 256 core of csrc/mfma_gemm.h with these three epilogues (mode 2 reads the old c in
+ * its epilogue).  The core addresses a and w with 32-bit byte offsets: M * K * 2 >= 2^32 or N * K * 2 >= 2^32 returns
+ * PPN_E_UNSUPPORTED (as ppn_gemm_bf16).  Bit-reproducible (no atomics). */
 int ppn_nat_gemm_bf16(const void* a, const void* w, const float* bias, const float* colsum, const float* stats_in, int32_t partials_in,
                       float* stats_out, void* c, int64_t M, int32_t N, int32_t K, int32_t mode, float eps, void* stream);
 

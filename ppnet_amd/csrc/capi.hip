@@ -646,42 +646,24 @@ int ppn_gemm_bf16(const void* a, const void* w, const float* bias, void* c, int6
 
 int ppn_nat_gemm_bf16(const void* a, const void* w, const float* bias, const float* colsum, const float* stats_in, int32_t partials_in,
                       float* stats_out, void* c, int64_t M, int32_t N, int32_t K, int32_t mode, float eps, void* stream) {
-    if (!a || !w || !c || !bias || M <= 0 || M >= (1LL << 31) || (M % 256) != 0 || N <= 0 || (N % 256) != 0 || K < 64 || (K % 64) != 0 ||
+    if (!a || !w || !c || !bias || M <= 0 || M >= (1LL << 31) || (M % 256) != 0 || N <= 0 || (N % 256) != 0 || K < 128 || (K % 64) != 0 ||
         mode < 0 || mode > 2)
         return PPN_E_INVALID;
     if (mode != 2 && (!colsum || !stats_in || partials_in < 1 || partials_in > 4 || K / 64 < 3)) return PPN_E_INVALID;
     if (mode == 2 && !stats_out) return PPN_E_INVALID;
-    if ((long long)N * 2 * 8 >= (1LL << 31) || (long long)K * 2 * 8 >= (1LL << 31)) return PPN_E_UNSUPPORTED;     // per-lane 32-bit offsets
-    // mode 2 (round 5): the 256 x 256 core of mfma_gemm.h with the old c read in its epilogue — faster than both round-4 forms on all six
-    // shapes (profiles/r05_natgemm_timing.txt); PPNET_NAT_ACC=old selects those (A/B)
-    static const bool acc_old = [] { const char* v = getenv("PPNET_NAT_ACC"); return v && v[0] == 'o'; }();
-    if (mode == 2 && !acc_old && K >= 128) {
-        const int n_cu = ppn::device_cu_count();
-        if (!n_cu) return hip_fail(hipErrorInvalidDevice);
-        const int e2 = ppn::gemm_acc_stats_launch(a, w, bias, stats_out, c, M, N, K, ppn::nat_gemm128_partials(N) ? 1 : 0, n_cu, (hipStream_t)stream);
-        if (e2 != 0) return hip_fail((hipError_t)e2);
-        return PPN_OK;
-    }
-    static const bool ln_old = [] { const char* v = getenv("PPNET_NAT_LN"); return v && v[0] == 'o'; }();
-    if (mode != 2 && !ln_old && K >= 128) {
-        const int n_cu = ppn::device_cu_count();
-        if (!n_cu) return hip_fail(hipErrorInvalidDevice);
-        const int e2 = ppn::gemm_ln_launch(a, w, bias, colsum, stats_in, partials_in, c, M, N, K, mode == 1, eps, n_cu, (hipStream_t)stream);
-        if (e2 != 0) return hip_fail((hipError_t)e2);
-        return PPN_OK;
-    }
-    // the HBM-bound levels (stream width <= 512) run on the small-tile kernel of nat_gemm128.hip, the rest on nat_gemm.hip's persistent one
-    const int e = ppn::nat_gemm128_wanted(N, K, mode)
-                      ? ppn::nat_gemm128_launch(a, w, bias, colsum, stats_in, partials_in, stats_out, c, M, N, K, mode, eps, (hipStream_t)stream)
-                      : ppn::nat_gemm_launch(a, w, bias, colsum, stats_in, partials_in, stats_out, c, M, N, K, mode, eps, (hipStream_t)stream);
-    if (e == -2) return hip_fail(hipErrorInvalidDevice);
+    if (M * K * 2 >= (1LL << 32) || (long long)N * K * 2 >= (1LL << 32)) return PPN_E_UNSUPPORTED;     // the core's 32-bit operand offsets
+    // the 256 x 256 core of mfma_gemm.h: mode 2 reads the old c in its epilogue, modes 0 / 1 fold the LayerNorm into theirs
+    const int n_cu = ppn::device_cu_count();
+    if (!n_cu) return hip_fail(hipErrorInvalidDevice);
+    const int e = mode == 2 ? ppn::gemm_acc_stats_launch(a, w, bias, stats_out, c, M, N, K, n_cu, (hipStream_t)stream)
+                            : ppn::gemm_ln_launch(a, w, bias, colsum, stats_in, partials_in, c, M, N, K, mode == 1, eps, n_cu, (hipStream_t)stream);
     if (e != 0) return hip_fail((hipError_t)e);
     return PPN_OK;
 }
 
 int32_t ppn_nat_gemm_partials(int32_t C) {
     if (C <= 0 || (C % 256) != 0) return -1;
-    return ppn::nat_gemm128_partials(C) ? C / 128 : C / 256;
+    return ppn::nat_stats_p128(C) ? C / 128 : C / 256;
 }
 
 int32_t ppn_nat_mlp_supported(int64_t M, int32_t C, int32_t HID) { return ppn::nat_mlp_supported(M, C, HID) ? 1 : 0; }

@@ -50,10 +50,10 @@ enum Epi {
                          // order by classify2_reduce_kernel: no atomics.  N <= 256: one slot, added straight onto the logits)
     EPI_ACCUM_STATS = 5, // C = C + acc + bias[n] in place, and (sum, sum of squares) of every row of the NEW C (of the bf16 values stored)
                          // per 128 or 256 columns -> stats[partial][m][2]: the accumulating projections of a NAT layer (proj, fc2:
-                         // SegNet/nat.py:145-153), whose row statistics the next LayerNorm-folded projection reads (nat_gemm.hip).
-                         // Persistent launches only.  Round 5: the old C is READ IN THE EPILOGUE — round 3-4's nat_gemm.hip fed it
+                         // SegNet/nat.py:145-153), whose row statistics the next LayerNorm-folded projection reads (EPI_LN_BIAS).
+                         // Persistent launches only.  Round 5: the old C is READ IN THE EPILOGUE — round 3-4's kernel (removed) fed it
                          // through the matrix pipe as four identity k-tiles (+25 ... +100 % MFMA and LDS work at K = 1024 ... 256)
-    EPI_LN_BIAS = 6,     // C = LN(A) W^T + b WITHOUT a LayerNorm pass (nat_gemm.hip's algebra): with B = W diag(gamma), bias = b + W beta,
+    EPI_LN_BIAS = 6,     // C = LN(A) W^T + b WITHOUT a LayerNorm pass: with B = W diag(gamma), bias = b + W beta,
     EPI_LN_BIAS_GELU = 7 // colsum[n] = sum_k B[n][k]:  C = rstd_m (acc - mean_m colsum[n]) + bias[n]  [then erf-GELU, logistic fit, |err| < 3e-5];
                          // mean / rstd of row m of A from the partial (sum, sum of squares) in stats[P][M][2] (EPI_ACCUM_STATS of the
                          // projection in front, the fused MLP kernel, or ppn_row_stats_bf16).  Persistent launches only.
@@ -90,7 +90,7 @@ __device__ __forceinline__ void glds16(const void* g, unsigned char* lds_uniform
 // erf-form GELU (torch.nn.GELU default).  erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, far below the bf16 rounding of
 // the result): one v_exp, one v_rcp and six FMAs instead of libm's ~40-instruction erff — the epilogue holds 128 values per lane.
 // 8-byte LDS accesses through the fragment element type: hipcc's waitcnt pass puts `s_waitcnt vmcnt(0)` in front of float2 / float4-
-// typed LDS accesses while an LDS-DMA is in flight (it cannot tell which bytes the DMA writes) and leaves these alone (nat_gemm.hip)
+// typed LDS accesses while an LDS-DMA is in flight (it cannot tell which bytes the DMA writes) and leaves these alone
 __device__ __forceinline__ float2 lds_f2(const void* ptr) { return __builtin_bit_cast(float2, *reinterpret_cast<const bf16x4*>(ptr)); }
 __device__ __forceinline__ void lds_st_f2(void* ptr, float2 v) { *reinterpret_cast<bf16x4*>(ptr) = __builtin_bit_cast(bf16x4, v); }
 
@@ -102,7 +102,7 @@ __device__ __forceinline__ float gelu_erf(float x) {
     return 0.5f * x + 0.5f * fabsf(x) * e;                            // 0.5 x (1 + sign(x) e)
 }
 
-// erf-GELU through a logistic fit of erf (nat_gemm.hip): x / (1 + 2^(-x (p0 + p1 x^2 + p2 x^4))), |error| < 3.0e-5
+// erf-GELU through a logistic fit of erf: x / (1 + 2^(-x (p0 + p1 x^2 + p2 x^4))), |error| < 3.0e-5 (tests/test_gpu_natgemm.py)
 __device__ __forceinline__ float gelu_logistic(float x) {
     const float x2 = fminf(x * x, 64.0f);
     const float t = x * (2.3009787f + x2 * (0.10690469f - 1.0350827e-3f * x2));
@@ -121,7 +121,7 @@ __device__ __forceinline__ f32x2 gelu_logistic2(f32x2 x) {               // two 
 
 // sum over the four lanes that share a row of the MFMA layout (lanes l, l ^ 16, l ^ 32, l ^ 48) on the vector ALU: v_permlane16/32_swap of a
 // value with itself leaves (even rows, odd rows) / (lower half, upper half) copies whose sum is the xor-16 / xor-32 partner sum — no
-// trip through the LDS crossbar (ds_bpermute) and no wait (nat_gemm.hip)
+// trip through the LDS crossbar (ds_bpermute) and no wait
 __device__ __forceinline__ float quad_sum(float v) {
     auto t = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     v = __uint_as_float(t[0]) + __uint_as_float(t[1]);
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_bf16_kernel(const Params p) 
         for (int e = 0; e < 8; ++e) { bq[e] = 0.f; cq[e] = 0.f; }
         // (what these loads and the queue drain in front of their first use cost was measured by building the epilogue without
         // them — wrong results, timing only: 1 us per tile, 0.23 ms per PPNet batch at most, profiles/r05_gemm_epilogue_loads.txt;
-        // staging them through LDS by DMA as nat_gemm.hip does would win back part of that and was not built)
+        // staging them through LDS by DMA beside the operands would win back part of that and was not built)
         if (EPI != EPI_ACCUM) {
             const float4 b0 = *reinterpret_cast<const float4*>(p.bias + n), b1 = *reinterpret_cast<const float4*>(p.bias + n + 4);
             bq[0] = b0.x; bq[1] = b0.y; bq[2] = b0.z; bq[3] = b0.w; bq[4] = b1.x; bq[5] = b1.y; bq[6] = b1.z; bq[7] = b1.w;

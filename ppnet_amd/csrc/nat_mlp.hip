@@ -88,7 +88,7 @@ struct Params {
 __device__ __forceinline__ void dma16(const void* base_uniform, unsigned off, unsigned lds_uniform) {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(off), "s"(base_uniform), "s"(lds_uniform) : "memory");
 }
-// erf-GELU through a logistic fit of erf (nat_gemm.hip: |error| < 3e-5), one v_exp + one v_rcp
+// erf-GELU through a logistic fit of erf (mfma_gemm.h's coefficients: |error| < 3e-5), one v_exp + one v_rcp
 __device__ __forceinline__ float gelu_logistic(float x) {
     const float x2 = fminf(x * x, 64.0f);
     const float t = x * (2.3009787f + x2 * (0.10690469f - 1.0350827e-3f * x2));

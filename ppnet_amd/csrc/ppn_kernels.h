@@ -159,19 +159,14 @@ int nat128_proj_add_launch(void* s, const void* a, const void* w, long long toke
 int gennet_trunk_launch(const void* x, void* y, const float* params, int B, int N, int n_blocks, hipStream_t stream);
 bool gemm_small_wanted(long long M, int N, int K);
 int gemm_small_launch(const void* a, const void* w, const float* bias, void* c, long long M, int N, int K, int epilogue, hipStream_t stream);
-bool nat_gemm128_wanted(int N, int K, int mode);
-bool nat_gemm128_partials(int C);
-int nat_gemm128_launch(const void* a, const void* w, const float* bias, const float* colsum, const float* stats_in, int p_in, float* stats_out,
-                       void* c, long long M, int N, int K, int mode, float eps, hipStream_t stream);
-int nat_gemm_launch(const void* a, const void* w, const float* bias, const float* colsum, const float* stats_in, int p_in,
-                    float* stats_out, void* c, long long M, int N, int K, int mode, float eps, hipStream_t stream);
-int row_stats_launch(const void* x, long long rows, int C, float* stats, hipStream_t stream);
 // nat_mlp.hip: the fused MLP of a NAT layer (LN -> fc1 -> GELU -> fc2 -> residual, hidden activation never leaves the CU)
 bool nat_mlp_supported(long long M, int C, int HID);
 int nat_mlp_pack_launch(const void* w1, const void* w2, void* wpk, int C, int HID, hipStream_t stream);
 int nat_mlp_launch(void* s, const void* wpk, const float* hb, const float* b2, float* stats_out, long long M, int C, int HID, float eps, hipStream_t stream);
-int gemm_acc_stats_launch(const void* a, const void* w, const float* bias, float* stats, void* c, long long M, int N, int K, int p128,
-                          int n_cu, hipStream_t stream);
+bool nat_stats_p128(int C);
+int row_stats_launch(const void* x, long long rows, int C, float* stats, hipStream_t stream);
+int gemm_acc_stats_launch(const void* a, const void* w, const float* bias, float* stats, void* c, long long M, int N, int K, int n_cu,
+                          hipStream_t stream);
 int gemm_ln_launch(const void* a, const void* w, const float* bias, const float* colsum, const float* stats, int parts, void* c, long long M,
                    int N, int K, int gelu, float eps, int n_cu, hipStream_t stream);
 int gemm_mfma_launch(const void* a, const void* w, const float* bias, void* c, long long M, int N, int K, int epi, int persistent,

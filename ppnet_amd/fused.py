@@ -448,7 +448,7 @@ def gemm_bf16(a, w, bias32, epilogue="bias", out=None, persistent_blocks=0):
 
 
 def nat_gemm(a, w, bias32, mode, out, colsum=None, stats_in=None, stats_out=None, eps=1e-5):
-    """The NAT projections with the LayerNorm / residual / statistics in the epilogue (ppn_nat_gemm_bf16, csrc/nat_gemm.hip).
+    """The NAT projections with the LayerNorm / residual / statistics in the epilogue (ppn_nat_gemm_bf16, csrc/mfma_gemm.h).
     mode "ln": out = LN(a) W0^T + b0 from the raw rows of a (w = W0 diag(gamma), bias32 = b0 + W0 beta, colsum, stats_in
     [P, M, 2]); "ln_gelu": gelu of that; "acc": out += a w^T + bias32 in place, row partials of the new out -> stats_out
     [nat_partials(N), M, 2]."""
@@ -505,17 +505,13 @@ def nat_mlp_(s2d, wpk, hb, b2, hidden, stats_out=None, eps=1e-5):
 
 
 def nat_partials(C):
-    """Row-statistics partials per row of a residual stream of width C (ppn_nat_gemm_partials: one per 128 columns up to
-    C = 256, one per 256 columns above — what the accumulating GEMM's epilogue emits and the LayerNorm-folding GEMM reads)."""
+    """Row-statistics partials per row of a residual stream of width C (ppn_nat_gemm_partials, csrc/mfma_gemm.hip: one per 128
+    columns up to C = 256, one per 256 columns above — what the accumulating GEMM's epilogue emits and the LayerNorm-folding GEMM
+    reads)."""
     n = L.lib.ppn_nat_gemm_partials(C)
     if n < 0:
         raise ValueError(f"ppn_nat_gemm_partials({C})")
     return n
-
-
-def nat_gemm_ok(M, N, K, acc):
-    """Shapes ppn_nat_gemm_bf16 serves: whole 256 x 256 tiles, at least three k-tiles in a tile (the accumulating mode adds four)."""
-    return M > 0 and M % 256 == 0 and N % 256 == 0 and K % 64 == 0 and (K // 64 + (4 if acc else 0)) >= 3
 
 
 def row_stats(x2d):

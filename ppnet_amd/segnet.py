@@ -337,7 +337,7 @@ class NATBlock(nn.Module):
         return (x, xo) if self.downsample is None else (self.downsample(x), xo)
 
     def _ln_folded_ok(self, x):
-        """The level runs on ppn_nat_gemm_bf16 (csrc/nat_gemm.hip): folded bfloat16 inference, C and the MLP width multiples of
+        """The level runs on ppn_nat_gemm_bf16 (csrc/mfma_gemm.h): folded bfloat16 inference, C and the MLP width multiples of
         256, whole 256-token tiles — and at least 64 of them in the narrowest projection (tokens x C): the persistent kernels walk
         256 x 256 tiles one per CU, and a batch of 1-16 problems has a handful (a level-2 projection at batch 1 is TWO tiles, each
         walking K alone: 34 us where the wave-per-block kernel of gemm_small.hip behind a LayerNorm launch takes 12)."""

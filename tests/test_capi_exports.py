@@ -76,6 +76,9 @@ def test_network_entry_points_reject_bad_arguments_without_gpu():
     assert L.ppn_upsample2x_add_nhwc(one, one, one, 1, 8, 8, 60, 1, None) == -1
     assert L.ppn_nat_mlp_bf16(None, one, one, one, None, 256, 256, 512, C.c_float(1e-5), None) == -1
     assert L.ppn_nat_mlp_supported(256, 512, 1024) == 0 and L.ppn_nat_mlp_supported(256, 256, 512) == 1
+    # ppn_nat_gemm_bf16(a, w, bias, colsum, stats_in, partials_in, stats_out, c, M, N, K, mode, eps, stream), mode 2
+    assert L.ppn_nat_gemm_bf16(one, one, one, one, one, 1, one, one, 256, 256, 64, 2, 1e-5, None) == -1            # K >= 128
+    assert L.ppn_nat_gemm_bf16(one, one, one, one, one, 1, one, one, 1 << 20, 256, 2048, 2, 1e-5, None) == -3      # M * K * 2 >= 2^32
 
 
 def test_polyfit_operator_matches_numpy():

@@ -1,4 +1,4 @@
-"""ppn_nat_gemm_bf16 (csrc/nat_gemm.hip): the NAT projections of DiNAT levels 1-3 with LayerNorm / residual / row statistics in the
+"""ppn_nat_gemm_bf16 (csrc/mfma_gemm.h): the NAT projections of DiNAT levels 1-3 with LayerNorm / residual / row statistics in the
 GEMM epilogues, against float64 compositions of the reference's ops on the same bfloat16 operands (SegNet/nat.py:62-85,140-153:
 norm -> qkv / fc1 (+ GELU); x + proj(...) / x + fc2(...)).  Tolerance: one bfloat16 rounding of the result (2^-8 relative) plus the
 float32 accumulation — stated per assertion."""
@@ -62,14 +62,14 @@ def test_ln_folded_projection_vs_float64(M, N, K, gelu):
                                    (16384, 512, 1024), (4096, 1024, 1024), (4096, 1024, 2048), (256 * 259, 512, 256), (768, 768, 192)])
 def test_accumulating_projection_and_row_partials(M, N, K):
     """mode 2: s += a W^T + b in place; stats_out[t] = (sum, sum of squares) of the new bfloat16 rows over tile column t (128 columns
-    for streams of width <= 512, else 256).  The old s is read in the epilogue and added in float32 (round 3-4: through the matrix
-    pipe, times an identity — equally exact), so the only roundings are the float32 accumulation and the final bfloat16 one."""
+    for streams of width <= 256, else 256).  The old s is read in the epilogue and added in float32 (round 3-4, since removed: through
+    the matrix pipe, times an identity — equally exact), so the only roundings are the float32 accumulation and the final bfloat16 one."""
     from ppnet_amd import fused
     a, w, b = _ops(M, N, K, 3)
     g = torch.Generator(device="cuda").manual_seed(4)
     s0 = (torch.randn(M, N, device="cuda", generator=g) * 2.0).to(torch.bfloat16)
     s = s0.clone()
-    P = fused.nat_partials(N)                                  # one partial per 128 columns (N <= 512) or per 256
+    P = fused.nat_partials(N)                                  # one partial per 128 columns (N <= 256) or per 256
     st = torch.full((P, M, 2), float("nan"), dtype=torch.float32, device="cuda")
     fused.nat_gemm(a, w, b, "acc", s, stats_out=st)
     ref = s0.double() + a.double() @ w.double().t() + b.double()
@@ -105,7 +105,7 @@ def test_chain_equals_layernorm_then_projection():
 
 def test_gelu_logistic_fit_of_erf():
     """The GELU of mode 1 is erf-GELU evaluated as x * sigmoid(x (p0 + p1 x^2 + p2 x^4)): the fit's error over the reals, in float64
-    with the kernel's coefficients (csrc/nat_gemm.hip gelu_logistic), stays below 3.1e-5 — 1 / 60 of a bfloat16 ulp at 1."""
+    with the kernel's coefficients (csrc/mfma_gemm.h gelu_logistic), stays below 3.1e-5 — 1 / 60 of a bfloat16 ulp at 1."""
     import math
     x = torch.linspace(-12, 12, 480001, dtype=torch.float64)
     x2 = torch.clamp(x * x, max=64.0)

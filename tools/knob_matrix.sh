@@ -27,14 +27,10 @@ run PPNET_NO_FOLD=1 $S
 run PPNET_NA_HALO16=0 tests/test_gpu_na.py $S
 run PPNET_NO_LN_FOLD=1 $S tests/test_gpu_natgemm.py
 run PPNET_LIBRARY_GEMM=1 $S
-run PPNET_NAT_GEMM128=0 $S tests/test_gpu_natgemm.py
-run PPNET_NAT_GEMM128=all $S tests/test_gpu_natgemm.py
 run PPNET_NO_SMALL_GEMM=1 $S tests/test_gpu_mfma.py
 run PPNET_NO_FUSED_MLP=1 $S tests/test_gpu_natgemm.py
 run PPNET_LIBRARY_GEMM_FROM_C=1073741824 $S
 run PPNET_LIBRARY_GEMM_FROM_C=1024 $S
 run PPNET_UPER_UNFUSED_RESIZE=1 tests/test_segnet.py
 run PPNET_NA_HALO_BLOCK=4x4 tests/test_gpu_na.py $S
-run PPNET_NAT_LN=old $S tests/test_gpu_natgemm.py
-run PPNET_NAT_ACC=old $S tests/test_gpu_natgemm.py
 exit $rc

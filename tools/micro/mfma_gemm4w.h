@@ -26,7 +26,7 @@
 // RAW (LDS-DMA -> ds_read): every wave's counted vmcnt precedes the barrier, the read follows it.  WAR (ds_read -> LDS-DMA): every
 // wave's lgkmcnt(0) precedes the barrier, the copy follows it.  Register sets: A0 always in fa[0], A1 in fa[1]; B0(g) in fb[g & 1],
 // B1(g) in fb[~g & 1] (the k-tile function is instantiated for both parities).  Vector-memory waits are counted at run time
-// (`issued - mark`, as in nat_gemm.hip): stores of an epilogue and copies share one in-order counter.
+// (`issued - mark`): stores of an epilogue and copies share one in-order counter.
 // The LDS image, XOR swizzle and fragment maps are mfma_gemm.h's (conflict-free ds_read_b128).
 //
 // RESULT (tools/micro/gemm4w_bench, one MI355X, random operands, both kernels alternating in one process; gpurun_out/r05/gemm4w_v1.txt,
