@@ -65,8 +65,8 @@ extern "C" {
  * before its first real call (ppnet_amd/_lib.py does, INTEGRATION.md shows the check) — argument lists are plain pointers and
  * sizes, so a caller built against another header would link and pass, say, a batch size where a workspace pointer is expected.
  * Bumped whenever an entry point's argument list changes or an entry point is removed: 100 = rounds 1-3; 101 = round 4
- * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5; 106 = ppn_swin_wmsa_fwd. */
-#define PPN_ABI_VERSION 106
+ * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5; 106 = ppn_swin_wmsa_fwd; 107 = ppn_upsample2x_concat_nhwc. */
+#define PPN_ABI_VERSION 107
 int         ppn_version(void);
 const char* ppn_error_string(int code);
 int         ppn_last_hip_error(void);   /* hipError_t of the most recent PPN_E_HIP on this thread */
@@ -327,6 +327,15 @@ int ppn_upsample2x_nhwc_bias(const void* x, const void* bias, void* y, int32_t B
  * mode='bilinear', align_corners=False)`) when the finer level is exactly twice the coarser one.  x [B][H][W][C], add and y
  * [B][2H][2W][C]; add may be y.  The resized value is rounded to the tensor's type before the sum, as the two separate kernels do. */
 int ppn_upsample2x_add_nhwc(const void* x, const void* add, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
+/* UPerPUPHead's FPN output assembly (SegNet/mmseg/decode_heads/uper_pup_head.py:121-128: the last `Upsample(scale_factor=2,
+ * mode='bilinear', align_corners=False)` of every FPN chain, then `torch.cat(fpn_outs, dim=1)`) in one pass: n <= 8 NHWC tensors
+ * x[l] [B][H][W][channels[l]] of ONE size (HOST arrays of pointers / channel counts; channels % 8 == 0), each up-sampled x2 with
+ * ppn_upsample2x_nhwc's arithmetic into channels [off_l, off_l + channels[l]) of out [B][2H][2W][sum channels], off_l the sum of the
+ * channels before it.  64-bit offsets: out may pass 2^32 bytes.  n outside 1..8, a NULL pointer, a bad size or dtype, or a grid past
+ * the launch limits (B (H + 1) >= 2^31; (W + 1) max(channels) / 8 > 65535 * 256) return PPN_E_INVALID before any HIP call.
+ * dtype 0 = float32, 1 = bfloat16. */
+int ppn_upsample2x_concat_nhwc(const void* const* x, const int32_t* channels, int32_t n, void* out, int32_t B, int32_t H, int32_t W, int32_t dtype,
+                               void* stream);
 /* UPerHead's FPN output assembly (mmseg/decode_heads/uper_head.py:117-127: `resize(fpn_outs[i], size=fpn_outs[0].shape[2:],
  * mode='bilinear', align_corners=False)` for i = 1..3, then `torch.cat(fpn_outs, dim=1)`) in one pass over NHWC tensors:
  * out [B][H0][W0][4 C], channels [l C, (l + 1) C) = level l resized to H0 x W0 (level 0 copied).  x_l is [B][hw[2 l]][hw[2 l + 1]][C]

@@ -425,6 +425,27 @@ int ppn_upsample2x_add_nhwc(const void* x, const void* add, void* y, int32_t B, 
     return PPN_OK;
 }
 
+int ppn_upsample2x_concat_nhwc(const void* const* x, const int32_t* channels, int32_t n, void* out, int32_t B, int32_t H, int32_t W, int32_t dtype,
+                               void* stream) {
+    if (!x || !channels || !out || n <= 0 || n > 8 || B <= 0 || H <= 0 || W <= 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;
+    int ch[8];
+    long long total = 0, cmax = 0;
+    for (int l = 0; l < n; ++l) {
+        if (!x[l] || channels[l] <= 0 || (channels[l] % 8) != 0) return PPN_E_INVALID;
+        ch[l] = channels[l];
+        total += channels[l];
+        cmax = channels[l] > cmax ? channels[l] : cmax;
+    }
+    // launch geometry (upsample2x_concat_launch): B (H + 1) block rows < 2^31, at most 65535 pieces of 256 threads per block row;
+    // 2H, 2W and the channel offsets stay 32-bit
+    if (total > 0x7fffffffLL || H >= (1 << 30) || W >= (1 << 30) || (long long)B * (H + 1) >= (1LL << 31) ||
+        (((long long)W + 1) * (cmax / 8) + 255) / 256 > 65535)
+        return PPN_E_INVALID;
+    const int e = ppn::upsample2x_concat_launch(x, ch, n, out, B, H, W, dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_resize_concat4_nhwc(const void* x0, const void* x1, const void* x2, const void* x3, const int32_t* hw, void* out, int32_t B, int32_t C,
                             int32_t dtype, void* stream) {
     if (!x0 || !x1 || !x2 || !x3 || !hw || !out || B <= 0 || C <= 0 || (C % 8) != 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;

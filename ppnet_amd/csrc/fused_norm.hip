@@ -146,9 +146,11 @@ template <typename T> __device__ __forceinline__ float through(float v);
 template <> __device__ __forceinline__ float through<float>(float v) { return v; }
 template <> __device__ __forceinline__ float through<__hip_bfloat16>(float v) { return __bfloat162float(__float2bfloat16(v)); }
 
+// The body of one thread, shared by upsample2x_kernel and upsample2x_concat_kernel: x [B][H][W][C] in, output pixels written to
+// y [B][2H][2W][Cy] at channels [yoff, yoff + C) (Cy = C, yoff = 0: a plain NHWC tensor).
 template <typename T, bool RELU>
-__global__ __launch_bounds__(256) void upsample2x_kernel(const T* __restrict__ x, const T* __restrict__ bias, const T* add, T* y, int B, int H, int W,
-                                                         int C) {
+__device__ __forceinline__ void upsample2x_block(const T* __restrict__ x, const T* __restrict__ bias, const T* add, T* y, int H, int W, int C,
+                                                 int Cy, int yoff) {
     // One thread per 8 channels of a 2 x 2 OUTPUT block {2i+1, 2i+2} x {2j+1, 2j+2}, i = -1 .. H-1, j = -1 .. W-1: its four pixels
     // interpolate the same 2 x 2 input block (rows i, i+1, columns j, j+1, clamped to the image), so a thread makes four 16-byte
     // loads for up to four 16-byte stores — one load per output instead of four (the pixel-per-thread form was bound by its
@@ -197,7 +199,7 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const T* __restrict__ x
             float o[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) o[k] = hy * (hx * v[0][0][k] + lx * v[0][1][k]) + ly * (hx * v[1][0][k] + lx * v[1][1][k]);
-            const size_t at = (((size_t)b * 2 * H + oy) * 2 * W + ox) * C + c0;
+            const size_t at = (((size_t)b * 2 * H + oy) * 2 * W + ox) * Cy + (yoff + c0);
             if (add) {                                                      // y = add + resize(x) (the FPN's top-down step, uper_head.py:103-108;
                 float ad[8];                                                // add may be y): the resized value rounds to T before the sum, as the
                 Vec8<T>::load(add + at, ad);                                // framework's two kernels leave it
@@ -207,6 +209,42 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const T* __restrict__ x
             Vec8<T>::store(y + at, o);
         }
     }
+}
+
+template <typename T, bool RELU>
+__global__ __launch_bounds__(256) void upsample2x_kernel(const T* __restrict__ x, const T* __restrict__ bias, const T* add, T* y, int B, int H, int W,
+                                                         int C) {
+    upsample2x_block<T, RELU>(x, bias, add, y, H, W, C, C, 0);
+}
+
+// The x2 up-sampling of n <= 8 NHWC tensors of one size [B][H][W][C_l] into their channel ranges of ONE output [B][2H][2W][Ctot]
+// (UPerPUPHead's last Upsample of every FPN chain + the torch.cat of the chains, uper_pup_head.py:121-128): the level is blockIdx.z
+// (uniform: its pointer, width and offset stay in scalars), a thread's work is upsample2x_kernel's.  Offsets are 64-bit: out may pass
+// 2^32 bytes.
+struct Up2xConcatParams {
+    const void* x[8];
+    int C[8], off[8];
+};
+template <typename T>
+__global__ __launch_bounds__(256) void upsample2x_concat_kernel(Up2xConcatParams p, T* y, int H, int W, int Ctot) {
+    const int l = (int)blockIdx.z;
+    upsample2x_block<T, false>(reinterpret_cast<const T*>(p.x[l]), nullptr, nullptr, y, H, W, p.C[l], Ctot, p.off[l]);
+}
+
+int upsample2x_concat_launch(const void* const* x, const int* ch, int n, void* y, int B, int H, int W, int dtype, hipStream_t stream) {
+    Up2xConcatParams p;
+    int off = 0, cmax = 0;
+    for (int l = 0; l < 8; ++l) {
+        const int k = l < n ? l : 0;
+        p.x[l] = x[k]; p.C[l] = ch[k]; p.off[l] = off;
+        if (l < n) { off += ch[l]; cmax = ch[l] > cmax ? ch[l] : cmax; }
+    }
+    const long long per_row = ((long long)W + 1) * (cmax / 8), rows = (long long)B * (H + 1);
+    if ((per_row + 255) / 256 > 65535 || rows >= (1LL << 31)) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)rows, (unsigned)((per_row + 255) / 256), (unsigned)n);
+    if (dtype == 0) hipLaunchKernelGGL(upsample2x_concat_kernel<float>, grid, dim3(256), 0, stream, p, (float*)y, H, W, off);
+    else hipLaunchKernelGGL(upsample2x_concat_kernel<__hip_bfloat16>, grid, dim3(256), 0, stream, p, (__hip_bfloat16*)y, H, W, off);
+    return (int)hipGetLastError();
 }
 
 int upsample2x_launch(const void* x, const void* bias, const void* add, void* y, int B, int H, int W, int C, int relu, int dtype, hipStream_t stream) {

@@ -178,6 +178,30 @@ def upsample2x_add_(fine, coarse):
     return fine
 
 
+def upsample2x_concat(levels):
+    """Up to eight channels_last [B,C_l,H,W] tensors of ONE size, each bilinearly up-sampled x2 (align_corners=False) into its channel
+    range of one output, in ONE kernel (ppn_upsample2x_concat_nhwc): UPerPUPHead's last Upsample of every FPN chain and the
+    concatenation behind them (uper_pup_head.py:121-128).  Returns a channels_last [B, sum C_l, 2H, 2W] tensor."""
+    assert 1 <= len(levels) <= 8
+    xs = []
+    for t in levels:
+        x = t.permute(0, 2, 3, 1)
+        xs.append(x if x.is_contiguous() else x.contiguous())
+    B, H, W, _ = xs[0].shape
+    if any(tuple(x.shape[:3]) != (B, H, W) for x in xs):
+        raise RuntimeError(f"upsample2x_concat: levels of different sizes {[tuple(x.shape[1:3]) for x in xs]}")
+    assert all(x.is_cuda and x.dtype == xs[0].dtype and x.shape[3] % 8 == 0 for x in xs) and xs[0].dtype in _DT
+    n = len(xs)
+    out = torch.empty(B, 2 * H, 2 * W, sum(x.shape[3] for x in xs), dtype=xs[0].dtype, device=xs[0].device)
+    ptrs = (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
+    ch = (ctypes.c_int32 * n)(*[x.shape[3] for x in xs])
+    with torch.cuda.device(out.device):
+        rc = L.lib.ppn_upsample2x_concat_nhwc(ptrs, ch, n, _p(out), B, H, W, _DT[xs[0].dtype],
+                                              ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream))
+    L.check(rc, "ppn_upsample2x_concat_nhwc")
+    return out.permute(0, 3, 1, 2)
+
+
 def resize_concat(levels):
     """Up to eight channels_last [B,C_l,H_l,W_l] tensors, each bilinearly resized (align_corners=False) to the FIRST one's size and
     concatenated over channels in ONE kernel (ppn_resize_concat_nhwc): UPerHead's FPN output assembly (uper_head.py:117-127) and

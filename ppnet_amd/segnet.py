@@ -587,17 +587,15 @@ class UPerHead(nn.Module):
         return (x.is_cuda and x.dtype == torch.bfloat16 and not self.training and all(isinstance(c.bn, nn.Identity) and c.conv.bias is not None for c in cms)
                 and self.conv_seg.out_channels == 2 and not fused.recording(x, self.conv_seg.weight) and not os.environ.get("PPNET_LIBRARY_CONV"))
 
-    def _forward_mfma(self, inputs):
-        """uper_head.py:76-127 with every convolution on the hand-written kernels: 1x1 ConvModules (laterals, pyramid pooling) are
-        ppn_gemm_bf16 over the NHWC tokens with bias + ReLU in the epilogue, 3x3 ConvModules the implicit-GEMM kernel
-        (ppn_conv3x3_mfma_bf16), the last one fused with the 1x1 classifier (ppn_conv3x3_relu_classify2_bf16: the 64-channel
-        activation at the highest resolution is never written); the FPN's top-down step, the resize + concatenation of its outputs
-        and the pyramid pooling module's pools and output assembly on NHWC kernels (ppn_upsample2x_add_nhwc, ppn_resize_concat_nhwc,
-        ppn_adaptive_pools_nhwc).  Nothing of the head runs on framework kernels but the 1x1 ConvModule of a pool scale with fewer
-        than 256 pooled positions in the batch."""
+    def _conv_modules(self):
+        return [m[1] for m in self.psp_modules] + [self.bottleneck] + list(self.lateral_convs) + list(self.fpn_convs) + [self.fpn_bottleneck]
+
+    def _mfma_packs(self):
+        """Every ConvModule's folded weight and bias in the layout its kernel reads (1x1: [Cout, Cin]; 3x3: _mfma_weights) and the
+        classifier's as float32 (key "seg"), keyed by module; rebuilt when a parameter changes."""
         if self._packs is None:
             self._packs = fused.WeightCache()
-        cms = [m[1] for m in self.psp_modules] + [self.bottleneck] + list(self.lateral_convs) + list(self.fpn_convs) + [self.fpn_bottleneck]
+        cms = self._conv_modules()
         src = [t for c in cms for t in (c.conv.weight, c.conv.bias)] + [self.conv_seg.weight, self.conv_seg.bias]
 
         def build():
@@ -611,36 +609,46 @@ class UPerHead(nn.Module):
             cs = self.conv_seg
             pk["seg"] = (cs.weight.detach().float().reshape(cs.out_channels, -1).contiguous(), cs.bias.detach().float().contiguous())
             return pk
-        pk = self._packs.get(src, build)
+        return self._packs.get(src, build)
 
-        def conv1(cm, t):                                                    # 1x1 ConvModule on a channels_last [B,C,H,W] tensor
-            Bn, Cc, Hh, Ww = t.shape
-            tok = t.permute(0, 2, 3, 1).reshape(-1, Cc)
-            w, b = pk[cm]
-            if tok.shape[0] >= 256 and Cc % 64 == 0 and Cc >= 128 and tok.is_contiguous():
-                y = fused.gemm_bf16(tok, w, b, "bias_relu")
-            else:                                                            # the pyramid's 1 .. 36 pooled positions per image: too few rows for a tile
-                y = F.relu(F.linear(tok, w, b.to(tok.dtype)))
-            return y.view(Bn, Hh, Ww, -1).permute(0, 3, 1, 2)
+    @staticmethod
+    def _mfma_conv1(pk, cm, t):
+        """1x1 ConvModule on a channels_last [B,C,H,W] tensor."""
+        Bn, Cc, Hh, Ww = t.shape
+        tok = t.permute(0, 2, 3, 1).reshape(-1, Cc)
+        w, b = pk[cm]
+        if tok.shape[0] >= 256 and Cc % 64 == 0 and Cc >= 128 and tok.is_contiguous():
+            y = fused.gemm_bf16(tok, w, b, "bias_relu")
+        else:                                                                # the pyramid's 1 .. 36 pooled positions per image: too few rows for a tile
+            y = F.relu(F.linear(tok, w, b.to(tok.dtype)))
+        return y.view(Bn, Hh, Ww, -1).permute(0, 3, 1, 2)
 
-        def conv3(cm, t, relu=True):
-            w, b = pk[cm]
-            if _use_mfma_conv(t, cm.conv, narrow=True):
-                return fused.conv3x3_mfma(t, w, b, stride=1, relu=relu)
-            y = F.conv2d(t, cm.conv.weight, cm.conv.bias, 1, 1)
-            return F.relu(y) if relu else y
+    @staticmethod
+    def _mfma_conv3(pk, cm, t, relu=True):
+        w, b = pk[cm]
+        if _use_mfma_conv(t, cm.conv, narrow=True):
+            return fused.conv3x3_mfma(t, w, b, stride=1, relu=relu)
+        y = F.conv2d(t, cm.conv.weight, cm.conv.bias, 1, 1)
+        return F.relu(y) if relu else y
+
+    def _own_resize(self):
+        return not self.align_corners and self.conv_seg.in_channels % 8 == 0 and not os.environ.get("PPNET_UPER_UNFUSED_RESIZE")
+
+    def _mfma_top_down(self, inputs, pk, own_resize):
+        """uper_head.py:76-108 on the build's kernels: the pyramid pooling module + bottleneck, the laterals and the top-down sums.
+        Returns the laterals, finest first, the last one the bottleneck's output."""
+        conv1, conv3 = self._mfma_conv1, self._mfma_conv3
         inputs = [inputs[i] for i in self.in_index]
         x = inputs[-1]
-        own_resize = not self.align_corners and self.conv_seg.in_channels % 8 == 0 and not os.environ.get("PPNET_UPER_UNFUSED_RESIZE")
         scales = [m[0].output_size if isinstance(m[0].output_size, int) else m[0].output_size[0] for m in self.psp_modules]
         if own_resize and len(scales) <= 4 and x.shape[1] % 8 == 0:
             # the pyramid pooling module (psp_head.py:48-60) as 6 launches: every pool in one kernel, a 1x1 ConvModule each on the
             # GEMM kernel (B s^2 rows), the resizes back + the concatenation with x in one kernel
             pooled = fused.adaptive_pools(x, scales)
-            psp = fused.resize_concat([x] + [conv1(m[1], t) for m, t in zip(self.psp_modules, pooled)])
+            psp = fused.resize_concat([x] + [conv1(pk, m[1], t) for m, t in zip(self.psp_modules, pooled)])
         else:
-            psp = torch.cat([x] + [self._resize(conv1(m[1], m[0](x)), x.shape[2:]) for m in self.psp_modules], dim=1).contiguous(memory_format=torch.channels_last)
-        laterals = [conv1(cm, inputs[i]) for i, cm in enumerate(self.lateral_convs)] + [conv3(self.bottleneck, psp)]
+            psp = torch.cat([x] + [self._resize(conv1(pk, m[1], m[0](x)), x.shape[2:]) for m in self.psp_modules], dim=1).contiguous(memory_format=torch.channels_last)
+        laterals = [conv1(pk, cm, inputs[i]) for i, cm in enumerate(self.lateral_convs)] + [conv3(pk, self.bottleneck, psp)]
         for i in range(len(laterals) - 1, 0, -1):
             fine, coarse = laterals[i - 1], laterals[i]
             if (own_resize and fine.shape[2] == 2 * coarse.shape[2] and fine.shape[3] == 2 * coarse.shape[3]
@@ -648,7 +656,20 @@ class UPerHead(nn.Module):
                 fused.upsample2x_add_(fine, coarse)                         # the resize and the sum: one kernel, in place
             else:
                 laterals[i - 1] = fine + self._resize(coarse, fine.shape[2:])
-        outs = [conv3(self.fpn_convs[i], laterals[i].contiguous(memory_format=torch.channels_last)) for i in range(len(laterals) - 1)] + [laterals[-1]]
+        return laterals
+
+    def _forward_mfma(self, inputs):
+        """uper_head.py:76-127 with every convolution on the hand-written kernels: 1x1 ConvModules (laterals, pyramid pooling) are
+        ppn_gemm_bf16 over the NHWC tokens with bias + ReLU in the epilogue, 3x3 ConvModules the implicit-GEMM kernel
+        (ppn_conv3x3_mfma_bf16), the last one fused with the 1x1 classifier (ppn_conv3x3_relu_classify2_bf16: the 64-channel
+        activation at the highest resolution is never written); the FPN's top-down step, the resize + concatenation of its outputs
+        and the pyramid pooling module's pools and output assembly on NHWC kernels (ppn_upsample2x_add_nhwc, ppn_resize_concat_nhwc,
+        ppn_adaptive_pools_nhwc).  Nothing of the head runs on framework kernels but the 1x1 ConvModule of a pool scale with fewer
+        than 256 pooled positions in the batch."""
+        pk = self._mfma_packs()
+        own_resize = self._own_resize()
+        laterals = self._mfma_top_down(inputs, pk, own_resize)
+        outs = [self._mfma_conv3(pk, self.fpn_convs[i], laterals[i].contiguous(memory_format=torch.channels_last)) for i in range(len(laterals) - 1)] + [laterals[-1]]
         if len(outs) == 4 and own_resize:
             cat = fused.resize_concat(outs)                                 # the three resizes + the concatenation: one kernel
         else:
@@ -659,7 +680,7 @@ class UPerHead(nn.Module):
             w, b = pk[fb]
             w2, b2 = pk["seg"]
             return fused.conv3x3_relu_classify2(cat, w, b, w2, b2).to(cat.dtype)
-        return self.conv_seg(conv3(fb, cat))
+        return self.conv_seg(self._mfma_conv3(pk, fb, cat))
 
     def forward(self, inputs):
         if self._prepared_mfma(inputs[self.in_index[-1]]):
@@ -673,6 +694,122 @@ class UPerHead(nn.Module):
         outs = [self.fpn_convs[i](laterals[i]) for i in range(len(laterals) - 1)] + [laterals[-1]]
         outs = [outs[0]] + [self._resize(o, outs[0].shape[2:]) for o in outs[1:]]
         return self.conv_seg(self.fpn_bottleneck(torch.cat(outs, dim=1)))
+
+
+class UPerPUPHead(UPerHead):
+    """The authors' UPerNet head with progressive up-sampling chains (SegNet/mmseg/decode_heads/uper_pup_head.py:12-131, the file
+    decode_heads/__init__.py:29 registers; over decode_head.py and psp_head.py): UPerHead's pyramid pooling, bottleneck, three lateral
+    1x1 convs and top-down sums, then on EVERY level, the pooling output included, a chain of num_convs[i] steps of 3x3 ConvModule +
+    bilinear x2 (`fpn_convs.i.j.0.{conv,bn}`), the four chain outputs concatenated, the 3x3 `fpn_bottleneck` and Dropout2d + the 1x1
+    `conv_seg`.  The chains must end at one size (num_convs[i] - i constant); otherwise the concatenation raises, as the reference's
+    torch.cat does.  The head of configs/nat/dense_nat_base.py and configs/swin/dense_swin_base.py."""
+
+    def __init__(self, in_channels=(128, 256, 512, 1024), channels=256, num_classes=2, num_convs=(2, 3, 4, 5), up_scale=2,
+                 pool_scales=(1, 2, 3, 6), in_index=(0, 1, 2, 3), dropout_ratio=0.1, align_corners=False, norm_cfg=None, **kwargs):
+        nn.Module.__init__(self)
+        assert len(num_convs) == len(in_channels) == len(in_index)
+        self.in_index, self.align_corners, self.num_convs = tuple(in_index), align_corners, tuple(num_convs)
+        # registration order = mmseg's state-dict order (BaseDecodeHead.__init__ makes conv_seg and dropout first, decode_head.py:102-106)
+        self.conv_seg = nn.Conv2d(channels, num_classes, 1)
+        self.dropout = nn.Dropout2d(dropout_ratio) if dropout_ratio > 0 else nn.Identity()
+        self.psp_modules = nn.ModuleList(
+            nn.Sequential(nn.AdaptiveAvgPool2d(ps), _ConvModule(in_channels[-1], channels, 1)) for ps in pool_scales)
+        self.bottleneck = _ConvModule(in_channels[-1] + len(pool_scales) * channels, channels, 3)
+        # uper_pup_head.py:48-77: four laterals are built and the last is dropped; a chain per level
+        self.lateral_convs = nn.ModuleList(_ConvModule(c, channels, 1) for c in in_channels[:-1])
+        self.fpn_convs = nn.ModuleList(
+            nn.ModuleList(nn.Sequential(_ConvModule(channels, channels, 3), _Upsample(up_scale, align_corners)) for _ in range(n))
+            for n in num_convs)
+        self.fpn_bottleneck = _ConvModule(len(in_channels) * channels, channels, 3)
+
+    def _conv_modules(self):
+        return ([m[1] for m in self.psp_modules] + [self.bottleneck] + list(self.lateral_convs)
+                + [step[0] for chain in self.fpn_convs for step in chain] + [self.fpn_bottleneck])
+
+    def _chains_x2(self, channels):
+        """Every chain non-empty and every step a bilinear x2 without align_corners: the NHWC up-sampling kernels apply."""
+        return (channels % 8 == 0 and all(len(chain) > 0 for chain in self.fpn_convs)
+                and all(step[1].scale_factor == 2.0 and not step[1].align_corners for chain in self.fpn_convs for step in chain))
+
+    def forward(self, inputs):
+        x = inputs[self.in_index[-1]]
+        if self._prepared_mfma(x) and self._chains_x2(self.conv_seg.in_channels):
+            return self._forward_mfma(inputs)
+        inputs = [inputs[i] for i in self.in_index]
+        x = inputs[-1]
+        laterals = [conv(inputs[i]) for i, conv in enumerate(self.lateral_convs)]
+        laterals.append(self.bottleneck(torch.cat([x] + [self._resize(m(x), x.shape[2:]) for m in self.psp_modules], dim=1)))
+        for i in range(len(laterals) - 1, 0, -1):                           # uper_pup_head.py:112-118
+            laterals[i - 1] = laterals[i - 1] + self._resize(laterals[i], laterals[i - 1].shape[2:])
+        ends = []
+        for i, chain in enumerate(self.fpn_convs):                          # uper_pup_head.py:121-126, all but each chain's last Upsample
+            t = laterals[i]
+            for j, step in enumerate(chain):
+                t = step[0](t)
+                if j + 1 < len(chain):
+                    t = step[1](t)
+            ends.append(t)
+        if (t.is_cuda and t.dtype in (torch.float32, torch.bfloat16) and self._chains_x2(t.shape[1])
+                and not fused.recording(t) and len({tuple(e.shape) for e in ends}) == 1):
+            cat = fused.upsample2x_concat(ends)                             # the last Upsample of every chain + torch.cat: one kernel
+        else:
+            cat = torch.cat([chain[-1][1](e) if len(chain) else e for chain, e in zip(self.fpn_convs, ends)], dim=1)
+        return self.conv_seg(self.dropout(self.fpn_bottleneck(cat)))        # cls_seg, decode_head.py:224-229
+
+    @staticmethod
+    def _mfma_conv1(pk, cm, t):
+        """UPerHead._mfma_conv1 with its few-row case (a pool scale with fewer than 256 pooled positions in the batch) in float32 with
+        the float32 bias, as ppn_gemm_bf16's epilogue adds it: which of the two a pool scale takes depends on the batch, and this way
+        the two differ only in the order of the float32 sums (the bfloat16 library call rounds the bias first)."""
+        Cc = t.shape[1]
+        if t.shape[0] * t.shape[2] * t.shape[3] >= 256 and Cc % 64 == 0 and Cc >= 128 and t.permute(0, 2, 3, 1).is_contiguous():
+            return UPerHead._mfma_conv1(pk, cm, t)
+        Bn, _, Hh, Ww = t.shape
+        w, b = pk[cm]
+        y = F.relu(F.linear(t.permute(0, 2, 3, 1).reshape(-1, Cc).float(), w.float(), b)).to(t.dtype)
+        return y.view(Bn, Hh, Ww, -1).permute(0, 3, 1, 2)
+
+    def _slice_images(self, inputs):
+        """Images per launch such that no operand of the 3x3 convolution kernel reaches 2^32 bytes (it addresses them with 32-bit byte
+        offsets, ppn_conv3x3_mfma_bf16 refuses larger ones): from the shapes of the bottleneck's input, every chain convolution's input
+        and the concatenation — the largest (33.5 MB per image for dense NAT at R = 256: batches of at most 127)."""
+        feats = [inputs[i] for i in self.in_index]
+        ch = self.conv_seg.in_channels
+        h, w = feats[-1].shape[2:]
+        per = [(feats[-1].shape[1] + len(self.psp_modules) * ch) * h * w]
+        for f, chain in zip(feats, self.fpn_convs):
+            h, w = f.shape[2:]
+            per += [ch * (h << j) * (w << j) for j in range(len(chain))]
+        h, w = feats[0].shape[2:]
+        per.append(len(self.fpn_convs) * ch * (h << self.num_convs[0]) * (w << self.num_convs[0]))
+        return max(1, (2 ** 32 - 1) // (max(per) * feats[0].element_size()))
+
+    def _forward_mfma(self, inputs):
+        """Prepared bfloat16 inference on the build's own kernels: the pyramid pooling, bottleneck, laterals and top-down sums as in
+        UPerHead._forward_mfma; every chain step one ppn_conv3x3_mfma_bf16 with the folded bias and the ReLU in its epilogue, then
+        ppn_upsample2x_nhwc — except the last step of every chain, whose up-sampling and the concatenation of the four chains are ONE
+        ppn_upsample2x_concat_nhwc; fpn_bottleneck + conv_seg one ppn_conv3x3_relu_classify2_bf16 (its 256-channel activation is
+        never written; its float32 logits are returned as they are).  Batches past _slice_images go through in equal slices."""
+        B = inputs[self.in_index[0]].shape[0]
+        bmax = self._slice_images(inputs)
+        if B > bmax:
+            step = -(-B // (-(-B // bmax)))                                   # equal slices
+            return torch.cat([self._forward_mfma([t[i:i + step] if t is not None else None for t in inputs]) for i in range(0, B, step)], dim=0)
+        pk = self._mfma_packs()
+        laterals = self._mfma_top_down(inputs, pk, self._own_resize())
+        ends = []
+        for lat, chain in zip(laterals, self.fpn_convs):
+            t = lat
+            for step in chain[:-1]:
+                t = fused.upsample2x_nhwc(self._mfma_conv3(pk, step[0], t))
+            ends.append(self._mfma_conv3(pk, chain[-1][0], t))
+        cat = fused.upsample2x_concat(ends)                                 # raises on chains of different lengths, as torch.cat does
+        fb = self.fpn_bottleneck
+        if _use_mfma_conv(cat, fb.conv, narrow=True):
+            w, b = pk[fb]
+            w2, b2 = pk["seg"]
+            return fused.conv3x3_relu_classify2(cat, w, b, w2, b2)
+        return self.conv_seg(self._mfma_conv3(pk, fb, cat))
 
 
 class FCNHead(nn.Module):
@@ -753,6 +890,35 @@ SWIN_BASE_UPER = dict(
         norm_cfg=_SWIN_NORM_CFG, align_corners=False, loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=0.4)),
     train_cfg=dict(), test_cfg=dict(mode="whole"))
 
+# The dense configs: UPerPUPHead (mmseg/decode_heads/uper_pup_head.py) on NAT-B and Swin-B.  `pretrained` (checkpoint paths on the
+# authors' machine, dense_nat_base.py:16, dense_swin_base.py:14) is left out, as in the SWIN_BASE_* dicts.
+_UPERPUP_AUX = dict(   # the base models' FCNHead (_base_/models/nat.py:22-34, swin.py:32-44) with in_channels=512, num_classes=2
+    # (dense_nat_base.py:31-34, dense_swin_base.py:30-33)
+    type="FCNHead", in_channels=512, in_index=2, channels=256, num_convs=1, concat_input=False, dropout_ratio=0.1, num_classes=2,
+    norm_cfg=_SWIN_NORM_CFG, align_corners=False, loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=0.4))
+
+NAT_BASE_UPERPUP = dict(   # SegNet/configs/nat/dense_nat_base.py:5-35 over _base_/models/nat.py:1-37
+    type="EncoderDecoder", pretrained=None,
+    backbone=dict(   # nat.py:6-21 with dense_nat_base.py:7-17
+        type="NAT", embed_dim=128, mlp_ratio=2.0, depths=[3, 4, 18, 5], num_heads=[4, 8, 16, 32], drop_path_rate=0.5, kernel_size=7,
+        out_indices=(0, 1, 2, 3), qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, in_patch_size=4, frozen_stages=-1,
+        layer_scale=1e-5),
+    decode_head=dict(   # dense_nat_base.py:18-30
+        type="UPerPUPHead", in_channels=[128, 256, 512, 1024], in_index=[0, 1, 2, 3], num_convs=(1, 2, 3, 4), pool_scales=(1, 2, 3, 6),
+        channels=256, dropout_ratio=0.1, num_classes=2, norm_cfg=_SWIN_NORM_CFG, align_corners=False,
+        loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0)),
+    auxiliary_head=dict(_UPERPUP_AUX),
+    train_cfg=dict(), test_cfg=dict(mode="whole"))
+
+SWIN_BASE_UPERPUP = dict(   # SegNet/configs/swin/dense_swin_base.py:5-34 over _base_/models/swin.py:1-47
+    type="EncoderDecoder", pretrained=None, backbone=dict(_SWIN_BASE_BACKBONE),   # dense_swin_base.py:7-16 = swin_base.py:7-15
+    decode_head=dict(   # dense_swin_base.py:17-29
+        type="UPerPUPHead", in_channels=[128, 256, 512, 1024], in_index=[0, 1, 2, 3], num_convs=(2, 3, 4, 5), pool_scales=(1, 2, 3, 6),
+        channels=256, dropout_ratio=0.1, num_classes=2, norm_cfg=_SWIN_NORM_CFG, align_corners=False,
+        loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0)),
+    auxiliary_head=dict(_UPERPUP_AUX),
+    train_cfg=dict(), test_cfg=dict(mode="whole"))
+
 IMG_MEAN = (123.675, 116.28, 103.53)       # _base_/datasets/planning_seg.py:12-13
 IMG_STD = (58.395, 57.12, 57.375)
 
@@ -772,7 +938,7 @@ class SegNet(nn.Module):
         self.backbone = {"NAT": NAT, "DiNAT": DiNAT, "SwinTransformer": SwinTransformer}[bb_type](**bb_cfg)
         head_cfg = dict(decode_head or DINAT_BASE["decode_head"])
         head_type = head_cfg.pop("type", "SETRUPHead")
-        self.decode_head = {"SETRUPHead": SETRUPHead, "UPerHead": UPerHead, "FCNHead": FCNHead}[head_type](**head_cfg)
+        self.decode_head = {"SETRUPHead": SETRUPHead, "UPerHead": UPerHead, "UPerPUPHead": UPerPUPHead, "FCNHead": FCNHead}[head_type](**head_cfg)
         self.auxiliary_head = None
         if auxiliary_head is not None:                                         # encoder_decoder.py:52-61 (a dict, or a list of them)
             mk = lambda c: FCNHead(**{k: v for k, v in dict(c).items() if k != "type"})
