@@ -65,8 +65,9 @@ extern "C" {
  * before its first real call (ppnet_amd/_lib.py does, INTEGRATION.md shows the check) — argument lists are plain pointers and
  * sizes, so a caller built against another header would link and pass, say, a batch size where a workspace pointer is expected.
  * Bumped whenever an entry point's argument list changes or an entry point is removed: 100 = rounds 1-3; 101 = round 4
- * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5; 106 = ppn_swin_wmsa_fwd; 107 = ppn_upsample2x_concat_nhwc. */
-#define PPN_ABI_VERSION 107
+ * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5; 106 = ppn_swin_wmsa_fwd; 107 = ppn_upsample2x_concat_nhwc;
+ * 108 = ppn_mhsa_fwd. */
+#define PPN_ABI_VERSION 108
 int         ppn_version(void);
 const char* ppn_error_string(int code);
 int         ppn_last_hip_error(void);   /* hipError_t of the most recent PPN_E_HIP on this thread */
@@ -282,6 +283,17 @@ int ppn_na2d_fwd_vpad(const void* qkv, const void* pad_kv, const float* rpb, voi
  * dtype 0 = float32, 1 = bfloat16 (float32 accumulation, matrix cores). */
 int ppn_swin_wmsa_fwd(const void* qkv, const void* pad_kv, const float* rpb, void* out, int32_t B, int32_t H, int32_t W,
                       int32_t heads, int32_t window, int32_t shift, float scale, int32_t dtype, void* stream);
+
+/* Global multi-head self-attention, forward (the body of nn.MultiheadAttention between in_proj and out_proj, which mmseg's
+ * VisionTransformer calls through mmcv's MultiheadAttention, SegNet/mmseg/backbones/vit.py:63-70,92-95):
+ * out[b][n][h][:] = softmax_m(scale * q[b][n][h] . k[b][m][h]) . v[b][m][h], the sum over all N keys m of image b.
+ * qkv [B][N][3][heads][head_dim] (each token row q | k | v: the order of in_proj_weight), out [B][N][heads][head_dim].
+ * head_dim must be 64 (else PPN_E_UNSUPPORTED); any N >= 1.  NULL pointers, B / N / heads <= 0, a non-finite or non-positive
+ * scale, a dtype other than 0 / 1, buffers not 16-byte aligned and grids of 2^31 work-items or more return PPN_E_INVALID
+ * before any HIP call.  dtype 0 = float32 (VALU), 1 = bfloat16 (flash-style on the matrix cores: float32 online softmax and
+ * accumulation, the output rounded once). */
+int ppn_mhsa_fwd(const void* qkv, void* out, int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, int32_t dtype,
+                 void* stream);
 
 /* Backward of ppn_na2d_fwd (the gradient NATTEN's natten2dqkrpb / natten2dav backward kernels compute; first brick of the
  * training step, GenNet/train.py:93-147, SegNet/mmseg/apis/train.py:67-167).  qkv [B][H][W][3][heads][32] and rpb as in the

@@ -375,6 +375,19 @@ int ppn_swin_wmsa_fwd(const void* qkv, const void* pad_kv, const float* rpb, voi
     return PPN_OK;
 }
 
+int ppn_mhsa_fwd(const void* qkv, void* out, int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, int32_t dtype,
+                 void* stream) {
+    if (!qkv || !out || B <= 0 || N <= 0 || heads <= 0 || head_dim <= 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;
+    if (!(scale > 0.0f) || scale > 3.0e38f) return PPN_E_INVALID;                        // NaN, inf, zero, negative
+    if (head_dim != 64) return PPN_E_UNSUPPORTED;
+    if ((((uintptr_t)qkv | (uintptr_t)out) & 15) != 0) return PPN_E_INVALID;              // 16-byte loads / stores
+    const long long qblock = dtype == 0 ? 64 : 128, threads = dtype == 0 ? 64 : 256;       // queries / work-items per workgroup
+    if ((long long)B * heads * ((N + qblock - 1) / qblock) * threads >= 0x7fffffffLL) return PPN_E_INVALID;
+    const int e = ppn::mhsa_launch(qkv, out, B, N, heads, scale, dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_residual_layernorm(const void* x, const void* a, const void* gamma, const void* w, const void* b, void* x_out,
                            void* y_out, int64_t rows, int32_t C, float eps, int32_t dtype, void* stream) {
     return ppn_residual_layernorm_padded(x, a, gamma, w, b, x_out, y_out, rows, C, eps, dtype, 0, 0, 0, 0, stream);

@@ -129,6 +129,24 @@ def layer_norm(x, ln, pad_to=None, offset=None):
     return y
 
 
+_LN_REFUSED = set()        # (width, dtype) pairs the LayerNorm kernels answered with PPN_E_UNSUPPORTED
+
+
+def layer_norm_any_width(x, ln):
+    """ln(x) over the last dimension on the LayerNorm kernel; a row width the kernel does not take (it answers PPN_E_UNSUPPORTED
+    before any launch: csrc/fused_norm.hip launch_norm, widths up to 512 and 1024 — not ViT-B's 768) runs on the framework's
+    LayerNorm instead, and the refusal is remembered."""
+    key = (x.shape[-1], x.dtype)
+    if key not in _LN_REFUSED:
+        try:
+            return layer_norm(x, ln)
+        except L.PpnError as e:
+            if e.code != L.PPN_E_UNSUPPORTED:
+                raise
+            _LN_REFUSED.add(key)
+    return F.layer_norm(x, ln.normalized_shape, ln.weight, ln.bias, ln.eps)
+
+
 def residual_layer_norm(x, a, gamma, ln_next, pad_to=None):
     """x' = x + gamma * a (gamma None = 1) in place of x; returns (x', ln_next(x')) — y is None when ln_next is None.
     (Under autograd x' is a new tensor.)"""

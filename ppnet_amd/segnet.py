@@ -17,6 +17,7 @@ import torch.nn.functional as F
 from . import fused
 from .na import NeighborhoodAttention2D
 from .swin import SwinTransformer
+from .vit import VisionTransformer
 
 
 def drop_path(x, rate, training):
@@ -498,7 +499,8 @@ class SETRUPHead(nn.Module):
         """lowres=True: the classifier's logits BEFORE the last x2 up-sampling (the caller fuses the rest of the tail)."""
         x = inputs[self.in_index]
         # LayerNorm over channels (setr_up_head.py:73-76) on the NHWC view; stays channels_last for the convolutions
-        x = fused.layer_norm(x.permute(0, 2, 3, 1), self.norm).permute(0, 3, 1, 2)
+        # (768-wide rows, ViT-B's, take the framework's LayerNorm: fused.layer_norm_any_width)
+        x = fused.layer_norm_any_width(x.permute(0, 2, 3, 1), self.norm).permute(0, 3, 1, 2)
         prepared = all(isinstance(up[0].bn, nn.Identity) and up[0].conv.bias is not None for up in self.up_convs)
         if prepared and all(_use_mfma_conv(x, up[0].conv) for up in self.up_convs) and self.conv_seg.out_channels == 2:
             return self._forward_mfma(x, lowres)
@@ -919,6 +921,23 @@ SWIN_BASE_UPERPUP = dict(   # SegNet/configs/swin/dense_swin_base.py:5-34 over _
     auxiliary_head=dict(_UPERPUP_AUX),
     train_cfg=dict(), test_cfg=dict(mode="whole"))
 
+# ViT-B/16 + SETR-UP: configs/vit/vit_base.py:1-30 names '../_base_/models/setr.py' (line 2), which the reference tree lacks; the
+# base model file that exists, _base_/models/vit.py:1-43, is that SETR model (EncoderDecoder + VisionTransformer + SETRUPHead with
+# the in_channels=768 of vit_base.py:26).  It cannot build alone (embed_dims=1024 with 12 heads, line 11-13), so it is merged here
+# with vit_base.py's overrides (lines 5-29): embed 768, 12 layers, 12 heads of 64, no cls token, patch 16.  `pretrained` (an
+# ImageNet checkpoint path on the authors' machine, vit_base.py:16) is left out: load one with VisionTransformer.init_weights.
+VIT_BASE_SETRUP = dict(
+    type="EncoderDecoder", pretrained=None,
+    backbone=dict(   # _base_/models/vit.py:6-17 with vit_base.py:7-16
+        type="VisionTransformer", img_size=224, patch_size=16, in_channels=3, embed_dims=768, num_layers=12, num_heads=12,
+        drop_rate=0.0, norm_cfg=dict(type="LN", eps=1e-6, requires_grad=True), with_cls_token=False),
+    decode_head=dict(   # _base_/models/vit.py:18-39 with vit_base.py:18-22
+        type="SETRUPHead", norm_layer=dict(type="LN", eps=1e-6, requires_grad=True), num_convs=4, up_scale=2, kernel_size=3,
+        init_cfg=[dict(type="Constant", val=1.0, bias=0, layer="LayerNorm"), dict(type="Normal", std=0.01, override=dict(name="conv_seg"))],
+        in_channels=768, channels=512, in_index=-1, num_classes=2, norm_cfg=dict(type="SyncBN", requires_grad=True), align_corners=False,
+        loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0)),
+    train_cfg=dict(), test_cfg=dict(mode="whole"))
+
 IMG_MEAN = (123.675, 116.28, 103.53)       # _base_/datasets/planning_seg.py:12-13
 IMG_STD = (58.395, 57.12, 57.375)
 
@@ -935,7 +954,8 @@ class SegNet(nn.Module):
         bb_type = bb_cfg.pop("type", "DiNAT")
         if pretrained is not None and bb_cfg.get("pretrained") is None:
             bb_cfg["pretrained"] = pretrained                                  # encoder_decoder.py:32-36
-        self.backbone = {"NAT": NAT, "DiNAT": DiNAT, "SwinTransformer": SwinTransformer}[bb_type](**bb_cfg)
+        self.backbone = {"NAT": NAT, "DiNAT": DiNAT, "SwinTransformer": SwinTransformer,
+                         "VisionTransformer": VisionTransformer}[bb_type](**bb_cfg)
         head_cfg = dict(decode_head or DINAT_BASE["decode_head"])
         head_type = head_cfg.pop("type", "SETRUPHead")
         self.decode_head = {"SETRUPHead": SETRUPHead, "UPerHead": UPerHead, "UPerPUPHead": UPerPUPHead, "FCNHead": FCNHead}[head_type](**head_cfg)
