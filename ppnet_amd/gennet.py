@@ -17,6 +17,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import fused
+from .dense import drop_path
+
 
 class _Attention(nn.Module):
     def __init__(self, dim, num_heads, qkv_bias=True):
@@ -53,7 +56,6 @@ class _Block(nn.Module):
         self.drop_path_rate = float(drop_path)    # stochastic depth, training only (vit.py:150,158-161)
 
     def forward(self, x):
-        from .segnet import drop_path
         x = x + drop_path(self.attn(_ln(x, self.norm1)), self.drop_path_rate, self.training)
         return x + drop_path(self.mlp(_ln(x, self.norm2)), self.drop_path_rate, self.training)
 
@@ -145,9 +147,8 @@ class _FusedStage(nn.Module):
     def __init__(self, conv, slope):
         super().__init__()
         self.conv, self.slope = conv, slope
-        from .fused import WeightCache
-        self._f32 = WeightCache()                         # (weight, bias) as float32 for the direct 1-channel kernel
-        self._s2 = WeightCache()                          # (packed weight, bias) for the MFMA stride-2 kernels
+        self._f32 = fused.WeightCache()                   # (weight, bias) as float32 for the direct 1-channel kernel
+        self._s2 = fused.WeightCache()                    # (packed weight, bias) for the MFMA stride-2 kernels
 
     def s2_pack(self):
         return self._s2.get((self.conv.weight, self.conv.bias), lambda: pack_s2_weights(self.conv))
@@ -159,20 +160,16 @@ class _FusedStage(nn.Module):
         if (isinstance(c, nn.Conv2d) and c.in_channels == 1 and c.out_channels <= 32 and c.kernel_size == (3, 3) and c.stride == (1, 1)
                 and c.padding == (1, 1) and c.dilation == (1, 1)):
             # 1 -> dim at full resolution: the direct HIP kernel (ppn_conv3x3_c1_nhwc), bias + LeakyReLU inside
-            from . import fused
             w32, b32 = self._f32.get((c.weight, c.bias), lambda: (c.weight.detach().float().contiguous(), c.bias.detach().float().contiguous()))
             return fused.conv3x3_c1(x, w32, b32, self.slope)
-        import os
         if x.dtype == torch.bfloat16 and _is_s2_stage(c) and x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0 and not os.environ.get("PPNET_LIBRARY_CONV"):
             # the 24-channel stride-2 stages: MFMA kernel with the weights in registers, bias + LeakyReLU in its epilogue
-            from . import fused
             wp, bp = self.s2_pack()
             return fused.gennet_conv_s2(x, wp, bp, self.slope, isinstance(c, nn.ConvTranspose2d))
         if isinstance(c, nn.ConvTranspose2d):
             y = F.conv_transpose2d(x, c.weight, None, c.stride, c.padding, c.output_padding, c.groups, c.dilation)
         else:
             y = F.conv2d(x, c.weight, None, c.stride, c.padding, c.dilation, c.groups)
-        from . import fused
         return fused.bias_act_(y.contiguous(memory_format=torch.channels_last), c.bias, self.slope)
 
 
@@ -181,7 +178,6 @@ def _ln(x, ln):
     # (tests/test_gennet_golden.py) check the module's wiring against the reference's own outputs without a GPU.  PPNet, the
     # drop-in classes and bench.py run on the GPU only, where every op below is a HIP kernel or a ROCm library call.
     if x.is_cuda:
-        from . import fused
         return fused.layer_norm(x, ln)                                       # thread-per-row HIP kernel (C = 24)
     return ln(x)
 
@@ -197,9 +193,8 @@ class AEViT(nn.Module):
         self.dec_conv = nn.ModuleList(_stage(nn.ConvTranspose2d(dim, dim, 3, 2, 1, output_padding=1)) for _ in range(n_down))
         self.conv_final = nn.Conv2d(dim, out_channels, 3, 1, 1)
         self._final_f32 = None                            # set by prepare_inference(): WeightCache of (float32 weight, float bias)
-        from .fused import WeightCache
-        self._trunk = WeightCache()                       # float32 parameter blocks of the fused ViT-trunk kernel
-        self._first_enc = WeightCache()                   # packed parameters of the fused first convolution + first encoder stage
+        self._trunk = fused.WeightCache()                 # float32 parameter blocks of the fused ViT-trunk kernel
+        self._first_enc = fused.WeightCache()             # packed parameters of the fused first convolution + first encoder stage
 
     def prepare_inference(self):
         """After the checkpoint is loaded: fold every eval-mode BatchNorm into the (transposed) convolution in front of
@@ -217,8 +212,7 @@ class AEViT(nn.Module):
         self.conv_first = _FusedStage(self.conv_first[0], self.conv_first[2].negative_slope)
         self.enc_conv = nn.ModuleList(_FusedStage(st[0], st[2].negative_slope) for st in self.enc_conv)
         self.dec_conv = nn.ModuleList(_FusedStage(st[0], st[2].negative_slope) for st in self.dec_conv)
-        from .fused import WeightCache
-        self._final_f32 = WeightCache()
+        self._final_f32 = fused.WeightCache()
         return self
 
     def _final_pack(self):
@@ -228,7 +222,6 @@ class AEViT(nn.Module):
 
     def _fused_first_stage(self, x):
         """Prepared bfloat16 inference: conv_first and enc_conv[0] as one kernel (ppn_gennet_first_enc_bf16), or None."""
-        import os
         cf = self.conv_first
         if not (isinstance(cf, _FusedStage) and len(self.enc_conv) > 0 and isinstance(self.enc_conv[0], _FusedStage) and x.is_cuda
                 and x.dtype == torch.bfloat16 and not os.environ.get("PPNET_GENNET_UNFUSED")):
@@ -238,7 +231,6 @@ class AEViT(nn.Module):
                 and c1.padding == (1, 1) and c1.bias is not None and isinstance(c2, nn.Conv2d) and _is_s2_stage(c2)
                 and x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0):
             return None
-        from . import fused
         packs = self._first_enc.get((c1.weight, c1.bias, c2.weight, c2.bias), lambda: pack_first_enc_weights(c1, c2))
         return fused.gennet_first_enc(x, *packs, cf.slope, self.enc_conv[0].slope)
 
@@ -253,11 +245,9 @@ class AEViT(nn.Module):
             for blk in self.enc_conv:
                 x = blk(x)
         B, C, H, W = x.shape
-        import os
         if (x.is_cuda and x.dtype == torch.bfloat16 and self._final_f32 is not None and C == 24 and H * W <= 1024 and (H * W) % 8 == 0
                 and self.vit_blocks[0].attn.num_heads == 3 and not os.environ.get("PPNET_LIBRARY_TRUNK")):
             # prepared bfloat16 inference: the three ViT blocks are one kernel (residual stream in registers, K / V in LDS)
-            from . import fused
             trunk = self._trunk.get(list(self.vit_blocks.parameters()), lambda: pack_trunk_params(self.vit_blocks).to(x.device))
             x = fused.gennet_trunk(x.contiguous(memory_format=torch.channels_last), trunk, len(self.vit_blocks))
         else:
@@ -270,7 +260,6 @@ class AEViT(nn.Module):
                 and not os.environ.get("PPNET_GENNET_UNFUSED_TAIL") and not os.environ.get("PPNET_LIBRARY_CONV")):
             # prepared bfloat16 inference: the last decoder stage and the final convolution are one kernel — the 24-channel tensor
             # at the output resolution never reaches memory (ppn_gennet_dec_final_bf16; bit-identical to the two kernels)
-            from . import fused
             for blk in self.dec_conv[:-1]:
                 x = blk(x)
             wp, bp = last.s2_pack()
@@ -279,8 +268,7 @@ class AEViT(nn.Module):
         for blk in self.dec_conv:
             x = blk(x)
         if x.is_cuda and self._final_f32 is not None and c.out_channels == 1 and c.in_channels % 8 == 0 and c.in_channels <= 32:
-            from . import fused                                               # dim -> 1 at full resolution: direct HIP kernel
-            wf, bf = self._final_pack()
+            wf, bf = self._final_pack()                                      # dim -> 1 at full resolution: direct HIP kernel
             return fused.conv3x3_to1(x, wf, bf)
         return c(x)
 

@@ -1,0 +1,420 @@
+"""SegNet's decode heads (reference SegNet/mmseg/decode_heads: setr_up_head.py:28-81, uper_head.py:12-127 + psp_head.py:10-60,
+uper_pup_head.py:12-131, fcn_head.py:11-81 over decode_head.py) as plain nn.Modules with mmseg's constructor arguments and
+checkpoint key names (`norm`, `up_convs.i.0.{conv,bn}`, `psp_modules.i.1.{conv,bn}`, `bottleneck`, `lateral_convs.i`, `fpn_convs.i`,
+`fpn_bottleneck`, `convs.i`, `conv_cat`, `conv_seg`), and BaseDecodeHead's losses.  Unprepared they are the reference's op chains
+through PyTorch; prepared bfloat16 inference on the GPU takes the build's own kernels (`_forward_mfma`) where dense.py lets it."""
+import os
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import fused
+from .dense import mfma_weights, use_mfma_conv
+
+
+class _ConvModule(nn.Sequential):
+    """mmcv ConvModule(conv -> bn -> ReLU) with its parameter names `conv.*`, `bn.*` (conv has no bias under a norm)."""
+
+    def __init__(self, cin, cout, k, dilation=1):
+        super().__init__()
+        self.add_module("conv", nn.Conv2d(cin, cout, k, 1, ((k - 1) // 2) * dilation, dilation, bias=False))
+        self.add_module("bn", nn.BatchNorm2d(cout))          # SyncBN reverts to BN outside distributed runs (SegNet/train.py:179-185)
+        self.add_module("activate", nn.ReLU(inplace=True))
+
+
+class _Upsample(nn.Module):
+    def __init__(self, scale_factor, align_corners=False):
+        super().__init__()
+        self.scale_factor, self.align_corners = float(scale_factor), align_corners
+
+    def forward(self, x, relu=False, bias=None):
+        if self.scale_factor == 2.0 and not self.align_corners and x.shape[1] % 8 == 0 and x.is_cuda:
+            return fused.upsample2x_nhwc(x, relu, bias)                      # HIP kernel, bias + ReLU folded into the loads
+        if bias is not None:
+            x = x + bias.view(1, -1, 1, 1)
+        if relu:
+            x = F.relu(x)
+        size = [int(t * self.scale_factor) for t in x.shape[-2:]]            # mmseg/ops/wrappers.py:43-51
+        return F.interpolate(x, size, None, "bilinear", self.align_corners)
+
+
+def _seg_pack(conv_seg):
+    """The 1x1 classifier as the classify kernels read it: (weight [classes, channels], bias), both float32."""
+    return conv_seg.weight.detach().float().reshape(conv_seg.out_channels, -1).contiguous(), conv_seg.bias.detach().float().contiguous()
+
+
+def _in_equal_slices(feats, bmax, run):
+    """run(feats) for a list of batched tensors (None entries stay None) with at most bmax images per call: a batch within bmax
+    goes through as it is, a larger one in equal slices whose results are concatenated (torch.cat is reached only then)."""
+    B = next(t for t in feats if t is not None).shape[0]
+    if B <= bmax:
+        return run(feats)
+    step = -(-B // (-(-B // bmax)))                                       # equal slices
+    return torch.cat([run([t[i:i + step] if t is not None else None for t in feats]) for i in range(0, B, step)], dim=0)
+
+
+class SETRUPHead(nn.Module):
+    def __init__(self, in_channels=1024, channels=512, num_classes=2, num_convs=1, up_scale=4, kernel_size=3,
+                 in_index=-1, dropout_ratio=0.1, align_corners=False, norm_layer=None, norm_cfg=None, **kwargs):
+        super().__init__()
+        assert kernel_size in (1, 3)
+        self.in_index, self.align_corners = in_index, align_corners
+        self.norm = nn.LayerNorm(in_channels, eps=1e-6)
+        self.up_convs = nn.ModuleList()
+        cin = in_channels
+        for _ in range(num_convs):
+            self.up_convs.append(nn.Sequential(_ConvModule(cin, channels, kernel_size), _Upsample(up_scale, align_corners)))
+            cin = channels
+        self.conv_seg = nn.Conv2d(channels, num_classes, 1)
+        self.dropout = nn.Dropout2d(dropout_ratio) if dropout_ratio > 0 else nn.Identity()   # decode_head.py cls_seg; identity in eval
+
+    def forward(self, inputs, lowres=False):
+        """lowres=True: the classifier's logits BEFORE the last x2 up-sampling (the caller fuses the rest of the tail)."""
+        x = inputs[self.in_index]
+        # LayerNorm over channels (setr_up_head.py:73-76) on the NHWC view; stays channels_last for the convolutions
+        # (768-wide rows, ViT-B's, take the framework's LayerNorm: fused.layer_norm_any_width)
+        x = fused.layer_norm_any_width(x.permute(0, 2, 3, 1), self.norm).permute(0, 3, 1, 2)
+        prepared = all(isinstance(up[0].bn, nn.Identity) and up[0].conv.bias is not None for up in self.up_convs)
+        if prepared and all(use_mfma_conv(x, up[0].conv) for up in self.up_convs) and self.conv_seg.out_channels == 2:
+            return self._forward_mfma(x, lowres)
+        for up in self.up_convs[:-1]:
+            cm = up[0]
+            if isinstance(cm.bn, nn.Identity) and cm.conv.bias is not None:  # prepared: the folded-BN bias rides in the upsample kernel
+                c = cm.conv
+                x = up[1](F.conv2d(x, c.weight, None, c.stride, c.padding), relu=True, bias=c.bias)
+            else:
+                x = up[1](cm.bn(cm.conv(x)), relu=True)                      # conv -> BN -> ReLU + x2 bilinear in one kernel
+        # last stage: conv_seg is a 1x1 convolution and bilinear interpolation is linear with weights summing to 1,
+        # so conv_seg(upsample(y)) == upsample(conv_seg(y)): classify at the low resolution and upsample 2 channels
+        # instead of `channels` (the reference materialises a [B,512,R/2,R/2] tensor here, setr_up_head.py:78-80)
+        conv, up = self.up_convs[-1][0], self.up_convs[-1][1]
+        if isinstance(conv.bn, nn.Identity) and conv.conv.bias is not None and x.is_cuda:
+            c = conv.conv                                                     # prepared: bias + ReLU in one in-place HIP pass
+            y = fused.bias_act_(F.conv2d(x, c.weight, None, c.stride, c.padding).contiguous(memory_format=torch.channels_last), c.bias, 0.0)
+        else:
+            y = conv(x)
+        if self.training:
+            # the reference's order (setr_up_head.py:78-80, decode_head.py:232-237): up-sample, channel dropout, classify —
+            # the dropout mask does not commute with the interpolation
+            return self.conv_seg(self.dropout(up(y)))
+        lo = self.conv_seg(y).contiguous()
+        return lo if lowres else up(lo)                                      # 2 channels: the library bilinear kernel
+
+    _mfma = None
+
+    def _forward_mfma(self, x, lowres):
+        """Prepared bfloat16 inference on the hand-written MFMA kernels: every ConvModule is one implicit-GEMM launch with the
+        folded-BatchNorm bias and the ReLU in its epilogue, and the last one also applies the 1x1 classifier (commuted in front
+        of the last up-sampling, as in forward()) so the 512-channel activation at the highest resolution is never written."""
+        if self._mfma is None:
+            self._mfma = fused.WeightCache()
+        cs = self.conv_seg
+        src = [t for up in self.up_convs for t in (up[0].conv.weight, up[0].conv.bias)] + [cs.weight, cs.bias]
+        packs = self._mfma.get(src, lambda: [mfma_weights(up[0].conv) for up in self.up_convs] + [_seg_pack(cs)])
+        n = len(self.up_convs) - 1
+
+        def run(feats):
+            x, = feats
+            for i, up in enumerate(self.up_convs[:-1]):
+                x = up[1](fused.conv3x3_mfma(x, packs[i][0], packs[i][1], stride=1, relu=True))
+            lo = fused.conv3x3_relu_classify2(x, *packs[n], *packs[-1]).to(x.dtype).contiguous()
+            return lo if lowres else self.up_convs[-1][1](lo)
+        # The convolution kernels address their input with 32-bit byte offsets: the last stage reads [B, channels, H 2^n, W 2^n]
+        # bfloat16, which passes 4 GiB at batch 256 of 512 x 512 maps.  Larger batches go through the head in slices.
+        last_in = self.up_convs[-1][0].conv.in_channels * x.shape[-2] * x.shape[-1] * 4 ** n * 2
+        return _in_equal_slices([x], max(1, (2 ** 32 - 1) // last_in), run)
+
+
+class UPerHead(nn.Module):
+    """UPerNet head (SegNet/mmseg/decode_heads/uper_head.py:12-127 + psp_head.py:10-60): pyramid pooling on the last level,
+    lateral 1x1 convs, top-down bilinear fusion, 3x3 FPN convs, concatenation, 3x3 bottleneck, 1x1 classifier.  Checkpoint
+    keys follow mmseg: `psp_modules.i.1.{conv,bn}`, `bottleneck.{conv,bn}`, `lateral_convs.i.{conv,bn}`,
+    `fpn_convs.i.{conv,bn}`, `fpn_bottleneck.{conv,bn}`, `conv_seg`.  The head of the reference's default SegNet config
+    (SegNet/test.py:29-32 -> configs/nat/upernet_nat_base.py)."""
+
+    def __init__(self, in_channels=(128, 256, 512, 1024), channels=64, num_classes=2, pool_scales=(1, 2, 3, 6),
+                 in_index=(0, 1, 2, 3), dropout_ratio=0.1, align_corners=False, norm_cfg=None, **kwargs):
+        super().__init__()
+        self.in_index, self.align_corners = tuple(in_index), align_corners
+        self.psp_modules = nn.ModuleList(
+            nn.Sequential(nn.AdaptiveAvgPool2d(ps), _ConvModule(in_channels[-1], channels, 1)) for ps in pool_scales)
+        self.bottleneck = _ConvModule(in_channels[-1] + len(pool_scales) * channels, channels, 3)
+        self.lateral_convs = nn.ModuleList(_ConvModule(c, channels, 1) for c in in_channels[:-1])
+        self.fpn_convs = nn.ModuleList(_ConvModule(channels, channels, 3) for _ in in_channels[:-1])
+        self.fpn_bottleneck = _ConvModule(len(in_channels) * channels, channels, 3)
+        self.conv_seg = nn.Conv2d(channels, num_classes, 1)                  # Dropout2d is the identity at inference
+
+    def _resize(self, x, size):
+        if (x.is_cuda and not self.align_corners and tuple(size) == (2 * x.shape[2], 2 * x.shape[3]) and x.shape[1] % 8 == 0
+                and x.dtype in (torch.float32, torch.bfloat16) and not fused.recording(x)):
+            return fused.upsample2x_nhwc(x)                                  # the FPN's x2 steps: the build's NHWC kernel
+        return F.interpolate(x, size=size, mode="bilinear", align_corners=self.align_corners)
+
+    _packs = None
+
+    def _prepared_mfma(self, x):
+        """Prepared bfloat16 inference on the build's own kernels: BatchNorm folded into every ConvModule (a bias on its conv)."""
+        cms = [m for m in self.modules() if isinstance(m, _ConvModule)]
+        return (x.is_cuda and x.dtype == torch.bfloat16 and not self.training and all(isinstance(c.bn, nn.Identity) and c.conv.bias is not None for c in cms)
+                and self.conv_seg.out_channels == 2 and not fused.recording(x, self.conv_seg.weight) and not os.environ.get("PPNET_LIBRARY_CONV"))
+
+    def _conv_modules(self):
+        return [m[1] for m in self.psp_modules] + [self.bottleneck] + list(self.lateral_convs) + list(self.fpn_convs) + [self.fpn_bottleneck]
+
+    def _mfma_packs(self):
+        """Every ConvModule's folded weight and bias in the layout its kernel reads (1x1: [Cout, Cin]; 3x3: mfma_weights) and the
+        classifier's as float32 (key "seg"), keyed by module; rebuilt when a parameter changes."""
+        if self._packs is None:
+            self._packs = fused.WeightCache()
+        cms = self._conv_modules()
+        src = [t for c in cms for t in (c.conv.weight, c.conv.bias)] + [self.conv_seg.weight, self.conv_seg.bias]
+
+        def build():
+            pk = {}
+            for c in cms:
+                cv = c.conv
+                if cv.kernel_size == (1, 1):
+                    pk[c] = (cv.weight.detach().reshape(cv.out_channels, cv.in_channels).contiguous(), cv.bias.detach().float().contiguous())
+                else:
+                    pk[c] = mfma_weights(cv)
+            pk["seg"] = _seg_pack(self.conv_seg)
+            return pk
+        return self._packs.get(src, build)
+
+    @staticmethod
+    def _mfma_conv1(pk, cm, t):
+        """1x1 ConvModule on a channels_last [B,C,H,W] tensor."""
+        Bn, Cc, Hh, Ww = t.shape
+        tok = t.permute(0, 2, 3, 1).reshape(-1, Cc)
+        w, b = pk[cm]
+        if tok.shape[0] >= 256 and Cc % 64 == 0 and Cc >= 128 and tok.is_contiguous():
+            y = fused.gemm_bf16(tok, w, b, "bias_relu")
+        else:                                                                # the pyramid's 1 .. 36 pooled positions per image: too few rows for a tile
+            y = F.relu(F.linear(tok, w, b.to(tok.dtype)))
+        return y.view(Bn, Hh, Ww, -1).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def _mfma_conv3(pk, cm, t, relu=True):
+        w, b = pk[cm]
+        if use_mfma_conv(t, cm.conv, narrow=True):
+            return fused.conv3x3_mfma(t, w, b, stride=1, relu=relu)
+        y = F.conv2d(t, cm.conv.weight, cm.conv.bias, 1, 1)
+        return F.relu(y) if relu else y
+
+    def _own_resize(self):
+        return not self.align_corners and self.conv_seg.in_channels % 8 == 0 and not os.environ.get("PPNET_UPER_UNFUSED_RESIZE")
+
+    def _mfma_top_down(self, inputs, pk, own_resize):
+        """uper_head.py:76-108 on the build's kernels: the pyramid pooling module + bottleneck, the laterals and the top-down sums.
+        Returns the laterals, finest first, the last one the bottleneck's output."""
+        conv1, conv3 = self._mfma_conv1, self._mfma_conv3
+        inputs = [inputs[i] for i in self.in_index]
+        x = inputs[-1]
+        scales = [m[0].output_size if isinstance(m[0].output_size, int) else m[0].output_size[0] for m in self.psp_modules]
+        if own_resize and len(scales) <= 4 and x.shape[1] % 8 == 0:
+            # the pyramid pooling module (psp_head.py:48-60) as 6 launches: every pool in one kernel, a 1x1 ConvModule each on the
+            # GEMM kernel (B s^2 rows), the resizes back + the concatenation with x in one kernel
+            pooled = fused.adaptive_pools(x, scales)
+            psp = fused.resize_concat([x] + [conv1(pk, m[1], t) for m, t in zip(self.psp_modules, pooled)])
+        else:
+            psp = torch.cat([x] + [self._resize(conv1(pk, m[1], m[0](x)), x.shape[2:]) for m in self.psp_modules], dim=1).contiguous(memory_format=torch.channels_last)
+        laterals = [conv1(pk, cm, inputs[i]) for i, cm in enumerate(self.lateral_convs)] + [conv3(pk, self.bottleneck, psp)]
+        for i in range(len(laterals) - 1, 0, -1):
+            fine, coarse = laterals[i - 1], laterals[i]
+            if (own_resize and fine.shape[2] == 2 * coarse.shape[2] and fine.shape[3] == 2 * coarse.shape[3]
+                    and fine.permute(0, 2, 3, 1).is_contiguous()):
+                fused.upsample2x_add_(fine, coarse)                         # the resize and the sum: one kernel, in place
+            else:
+                laterals[i - 1] = fine + self._resize(coarse, fine.shape[2:])
+        return laterals
+
+    def _forward_mfma(self, inputs):
+        """uper_head.py:76-127 with every convolution on the hand-written kernels: 1x1 ConvModules (laterals, pyramid pooling) are
+        ppn_gemm_bf16 over the NHWC tokens with bias + ReLU in the epilogue, 3x3 ConvModules the implicit-GEMM kernel
+        (ppn_conv3x3_mfma_bf16), the last one fused with the 1x1 classifier (ppn_conv3x3_relu_classify2_bf16: the 64-channel
+        activation at the highest resolution is never written); the FPN's top-down step, the resize + concatenation of its outputs
+        and the pyramid pooling module's pools and output assembly on NHWC kernels (ppn_upsample2x_add_nhwc, ppn_resize_concat_nhwc,
+        ppn_adaptive_pools_nhwc).  Nothing of the head runs on framework kernels but the 1x1 ConvModule of a pool scale with fewer
+        than 256 pooled positions in the batch."""
+        pk = self._mfma_packs()
+        own_resize = self._own_resize()
+        laterals = self._mfma_top_down(inputs, pk, own_resize)
+        outs = [self._mfma_conv3(pk, self.fpn_convs[i], laterals[i].contiguous(memory_format=torch.channels_last)) for i in range(len(laterals) - 1)] + [laterals[-1]]
+        if len(outs) == 4 and own_resize:
+            cat = fused.resize_concat(outs)                                 # the three resizes + the concatenation: one kernel
+        else:
+            outs = [outs[0]] + [self._resize(o, outs[0].shape[2:]) for o in outs[1:]]
+            cat = torch.cat(outs, dim=1).contiguous(memory_format=torch.channels_last)
+        fb = self.fpn_bottleneck
+        if use_mfma_conv(cat, fb.conv, narrow=True):
+            return fused.conv3x3_relu_classify2(cat, *pk[fb], *pk["seg"]).to(cat.dtype)
+        return self.conv_seg(self._mfma_conv3(pk, fb, cat))
+
+    def _top_down(self, inputs):
+        """uper_head.py:76-108 (= uper_pup_head.py:88-118) as the reference composes it: the pyramid pooling module + bottleneck, the
+        laterals and the top-down sums.  Returns the laterals, finest first, the last one the bottleneck's output."""
+        inputs = [inputs[i] for i in self.in_index]
+        x = inputs[-1]
+        psp = torch.cat([x] + [self._resize(m(x), x.shape[2:]) for m in self.psp_modules], dim=1)
+        laterals = [conv(inputs[i]) for i, conv in enumerate(self.lateral_convs)] + [self.bottleneck(psp)]
+        for i in range(len(laterals) - 1, 0, -1):
+            laterals[i - 1] = laterals[i - 1] + self._resize(laterals[i], laterals[i - 1].shape[2:])
+        return laterals
+
+    def forward(self, inputs):
+        if self._prepared_mfma(inputs[self.in_index[-1]]):
+            return self._forward_mfma(inputs)
+        laterals = self._top_down(inputs)
+        outs = [self.fpn_convs[i](laterals[i]) for i in range(len(laterals) - 1)] + [laterals[-1]]
+        outs = [outs[0]] + [self._resize(o, outs[0].shape[2:]) for o in outs[1:]]
+        return self.conv_seg(self.fpn_bottleneck(torch.cat(outs, dim=1)))
+
+
+class UPerPUPHead(UPerHead):
+    """The authors' UPerNet head with progressive up-sampling chains (SegNet/mmseg/decode_heads/uper_pup_head.py:12-131, the file
+    decode_heads/__init__.py:29 registers; over decode_head.py and psp_head.py): UPerHead's pyramid pooling, bottleneck, three lateral
+    1x1 convs and top-down sums, then on EVERY level, the pooling output included, a chain of num_convs[i] steps of 3x3 ConvModule +
+    bilinear x2 (`fpn_convs.i.j.0.{conv,bn}`), the four chain outputs concatenated, the 3x3 `fpn_bottleneck` and Dropout2d + the 1x1
+    `conv_seg`.  The chains must end at one size (num_convs[i] - i constant); otherwise the concatenation raises, as the reference's
+    torch.cat does.  The head of configs/nat/dense_nat_base.py and configs/swin/dense_swin_base.py."""
+
+    def __init__(self, in_channels=(128, 256, 512, 1024), channels=256, num_classes=2, num_convs=(2, 3, 4, 5), up_scale=2,
+                 pool_scales=(1, 2, 3, 6), in_index=(0, 1, 2, 3), dropout_ratio=0.1, align_corners=False, norm_cfg=None, **kwargs):
+        nn.Module.__init__(self)
+        assert len(num_convs) == len(in_channels) == len(in_index)
+        self.in_index, self.align_corners, self.num_convs = tuple(in_index), align_corners, tuple(num_convs)
+        # registration order = mmseg's state-dict order (BaseDecodeHead.__init__ makes conv_seg and dropout first, decode_head.py:102-106)
+        self.conv_seg = nn.Conv2d(channels, num_classes, 1)
+        self.dropout = nn.Dropout2d(dropout_ratio) if dropout_ratio > 0 else nn.Identity()
+        self.psp_modules = nn.ModuleList(
+            nn.Sequential(nn.AdaptiveAvgPool2d(ps), _ConvModule(in_channels[-1], channels, 1)) for ps in pool_scales)
+        self.bottleneck = _ConvModule(in_channels[-1] + len(pool_scales) * channels, channels, 3)
+        # uper_pup_head.py:48-77: four laterals are built and the last is dropped; a chain per level
+        self.lateral_convs = nn.ModuleList(_ConvModule(c, channels, 1) for c in in_channels[:-1])
+        self.fpn_convs = nn.ModuleList(
+            nn.ModuleList(nn.Sequential(_ConvModule(channels, channels, 3), _Upsample(up_scale, align_corners)) for _ in range(n))
+            for n in num_convs)
+        self.fpn_bottleneck = _ConvModule(len(in_channels) * channels, channels, 3)
+
+    def _conv_modules(self):
+        return ([m[1] for m in self.psp_modules] + [self.bottleneck] + list(self.lateral_convs)
+                + [step[0] for chain in self.fpn_convs for step in chain] + [self.fpn_bottleneck])
+
+    def _chains_x2(self, channels):
+        """Every chain non-empty and every step a bilinear x2 without align_corners: the NHWC up-sampling kernels apply."""
+        return (channels % 8 == 0 and all(len(chain) > 0 for chain in self.fpn_convs)
+                and all(step[1].scale_factor == 2.0 and not step[1].align_corners for chain in self.fpn_convs for step in chain))
+
+    def forward(self, inputs):
+        x = inputs[self.in_index[-1]]
+        if self._prepared_mfma(x) and self._chains_x2(self.conv_seg.in_channels):
+            return self._forward_mfma(inputs)
+        laterals = self._top_down(inputs)                                   # uper_pup_head.py:88-118
+        ends = []
+        for i, chain in enumerate(self.fpn_convs):                          # uper_pup_head.py:121-126, all but each chain's last Upsample
+            t = laterals[i]
+            for j, step in enumerate(chain):
+                t = step[0](t)
+                if j + 1 < len(chain):
+                    t = step[1](t)
+            ends.append(t)
+        if (t.is_cuda and t.dtype in (torch.float32, torch.bfloat16) and self._chains_x2(t.shape[1])
+                and not fused.recording(t) and len({tuple(e.shape) for e in ends}) == 1):
+            cat = fused.upsample2x_concat(ends)                             # the last Upsample of every chain + torch.cat: one kernel
+        else:
+            cat = torch.cat([chain[-1][1](e) if len(chain) else e for chain, e in zip(self.fpn_convs, ends)], dim=1)
+        return self.conv_seg(self.dropout(self.fpn_bottleneck(cat)))        # cls_seg, decode_head.py:224-229
+
+    @staticmethod
+    def _mfma_conv1(pk, cm, t):
+        """UPerHead._mfma_conv1 with its few-row case (a pool scale with fewer than 256 pooled positions in the batch) in float32 with
+        the float32 bias, as ppn_gemm_bf16's epilogue adds it: which of the two a pool scale takes depends on the batch, and this way
+        the two differ only in the order of the float32 sums (the bfloat16 library call rounds the bias first)."""
+        Cc = t.shape[1]
+        if t.shape[0] * t.shape[2] * t.shape[3] >= 256 and Cc % 64 == 0 and Cc >= 128 and t.permute(0, 2, 3, 1).is_contiguous():
+            return UPerHead._mfma_conv1(pk, cm, t)
+        Bn, _, Hh, Ww = t.shape
+        w, b = pk[cm]
+        y = F.relu(F.linear(t.permute(0, 2, 3, 1).reshape(-1, Cc).float(), w.float(), b)).to(t.dtype)
+        return y.view(Bn, Hh, Ww, -1).permute(0, 3, 1, 2)
+
+    def _slice_images(self, inputs):
+        """Images per launch such that no operand of the 3x3 convolution kernel reaches 2^32 bytes (it addresses them with 32-bit byte
+        offsets, ppn_conv3x3_mfma_bf16 refuses larger ones): from the shapes of the bottleneck's input, every chain convolution's input
+        and the concatenation — the largest (33.5 MB per image for dense NAT at R = 256: batches of at most 127)."""
+        feats = [inputs[i] for i in self.in_index]
+        ch = self.conv_seg.in_channels
+        h, w = feats[-1].shape[2:]
+        per = [(feats[-1].shape[1] + len(self.psp_modules) * ch) * h * w]
+        for f, chain in zip(feats, self.fpn_convs):
+            h, w = f.shape[2:]
+            per += [ch * (h << j) * (w << j) for j in range(len(chain))]
+        h, w = feats[0].shape[2:]
+        per.append(len(self.fpn_convs) * ch * (h << self.num_convs[0]) * (w << self.num_convs[0]))
+        return max(1, (2 ** 32 - 1) // (max(per) * feats[0].element_size()))
+
+    def _forward_mfma(self, inputs):
+        """Prepared bfloat16 inference on the build's own kernels: the pyramid pooling, bottleneck, laterals and top-down sums as in
+        UPerHead._forward_mfma; every chain step one ppn_conv3x3_mfma_bf16 with the folded bias and the ReLU in its epilogue, then
+        ppn_upsample2x_nhwc — except the last step of every chain, whose up-sampling and the concatenation of the four chains are ONE
+        ppn_upsample2x_concat_nhwc; fpn_bottleneck + conv_seg one ppn_conv3x3_relu_classify2_bf16 (its 256-channel activation is
+        never written; its float32 logits are returned as they are).  Batches past _slice_images go through in equal slices."""
+        return _in_equal_slices(inputs, self._slice_images(inputs), self._mfma_slice)
+
+    def _mfma_slice(self, inputs):
+        pk = self._mfma_packs()
+        laterals = self._mfma_top_down(inputs, pk, self._own_resize())
+        ends = []
+        for lat, chain in zip(laterals, self.fpn_convs):
+            t = lat
+            for step in chain[:-1]:
+                t = fused.upsample2x_nhwc(self._mfma_conv3(pk, step[0], t))
+            ends.append(self._mfma_conv3(pk, chain[-1][0], t))
+        cat = fused.upsample2x_concat(ends)                                 # raises on chains of different lengths, as torch.cat does
+        fb = self.fpn_bottleneck
+        if use_mfma_conv(cat, fb.conv, narrow=True):
+            return fused.conv3x3_relu_classify2(cat, *pk[fb], *pk["seg"])
+        return self.conv_seg(self._mfma_conv3(pk, fb, cat))
+
+
+class FCNHead(nn.Module):
+    """mmseg's FCNHead (SegNet/mmseg/decode_heads/fcn_head.py:11-81 over decode_head.py:54-107,224-229) — the auxiliary head of
+    the reference's NAT training configs (configs/_base_/models/nat.py:22-35, configs/nat/setr_up_nat_base.py:39-42: level 2,
+    512 -> 256 channels, one 3x3 conv-BN-ReLU, Dropout2d(0.1), 1x1 classifier, loss weight 0.4).  Checkpoint keys follow mmseg:
+    `convs.i.{conv,bn}`, `conv_cat.{conv,bn}`, `conv_seg`.  Training only: inference never evaluates it (encoder_decoder.py:63-80)."""
+
+    def __init__(self, in_channels=256, channels=256, num_classes=19, num_convs=2, kernel_size=3, concat_input=True, dilation=1,
+                 in_index=-1, dropout_ratio=0.1, align_corners=False, norm_cfg=None, loss_decode=None, **kwargs):
+        super().__init__()
+        assert num_convs >= 0 and dilation > 0
+        self.in_index, self.align_corners, self.concat_input = in_index, align_corners, concat_input
+        self.loss_weight = float((loss_decode or {}).get("loss_weight", 1.0))
+        if num_convs == 0:
+            assert in_channels == channels
+            self.convs = nn.Identity()
+        else:
+            self.convs = nn.Sequential(*[_ConvModule(in_channels if i == 0 else channels, channels, kernel_size, dilation)
+                                         for i in range(num_convs)])
+        if concat_input:
+            self.conv_cat = _ConvModule(in_channels + channels, channels, kernel_size)
+        self.conv_seg = nn.Conv2d(channels, num_classes, 1)
+        self.dropout = nn.Dropout2d(dropout_ratio) if dropout_ratio > 0 else nn.Identity()
+
+    def forward(self, inputs):
+        x = inputs[self.in_index]
+        y = self.convs(x)
+        if self.concat_input:
+            y = self.conv_cat(torch.cat([x, y], dim=1))
+        return self.conv_seg(self.dropout(y))
+
+
+def decode_losses(logit, gt, loss_weight=1.0, ignore_index=255):
+    """(loss_ce, acc_seg) of BaseDecodeHead.losses (decode_head.py:231-265) for resized logits [B,C,H,W] and labels [B,H,W].
+    mmseg's CrossEntropyLoss is F.cross_entropy(reduction='none', ignore_index) followed by a mean over ALL pixels — ignored
+    ones contribute 0 to the sum and still count in the divisor (losses/cross_entropy_loss.py:20-31, losses/utils.py:66-68);
+    accuracy() is called without an ignore index and divides by target.numel() (decode_head.py:264, losses/accuracy.py:39-49)."""
+    loss = loss_weight * F.cross_entropy(logit, gt, ignore_index=ignore_index, reduction="none").mean()
+    with torch.no_grad():
+        acc = (logit.argmax(1) == gt).float().sum() * (100.0 / gt.numel())
+    return loss, acc

@@ -4,7 +4,7 @@ relative_position_bias_table,relative_position_index},norm2,ffn.layers.{0.0,1}}`
 `norm{i}`), so an mmseg Swin checkpoint loads unchanged.
 
 Two forms of the same arithmetic:
-* GPU inference (CUDA tensors, no autograd): LayerNorm kernels, the build's GEMMs where their gates pass (segnet._linear) and the
+* GPU inference (CUDA tensors, no autograd): LayerNorm kernels, the build's GEMMs where their gates pass (dense.linear) and the
   fused (shifted-)window attention kernel ppn_swin_wmsa_fwd between the qkv and proj projections.
 * everything else (CPU, grad-enabled training on the GPU): a pure-torch composition of mmseg's ops (`window_attention`).
 """
@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import fused
+from .dense import IMG_MEAN, IMG_STD, drop_path, gpu_inference, linear
 
 WINDOW = 7
 HEAD_DIM = 32
@@ -25,11 +26,6 @@ CALLS = {"kernel": 0, "torch": 0}
 # Measurement hook like na.TIMING: a list here makes every kernel launch record (start event, end event, real tokens, channels,
 # element size).
 TIMING = None
-
-
-def _drop_path(x, rate, training):
-    from .segnet import drop_path
-    return drop_path(x, rate, training)
 
 
 def padded_hw(H, W, window=WINDOW):
@@ -129,10 +125,6 @@ def wmsa_forward(qkv, pad_kv, rpb_hw, heads, shift, scale, window=WINDOW):
     return out
 
 
-def _gpu_inference(x):
-    return x.is_cuda and not torch.is_grad_enabled()
-
-
 class WindowMSA(nn.Module):
     """swin.py:22-124: parameters qkv, proj, relative_position_bias_table [(2w-1)^2, heads], buffer relative_position_index."""
 
@@ -177,7 +169,7 @@ class ShiftWindowMSA(nn.Module):
     def attend(self, qkv):
         """Attention of qkv [B,H,W,3C] (before proj): the HIP kernel for GPU inference, the torch composition otherwise."""
         m = self.w_msa
-        if _gpu_inference(qkv):
+        if gpu_inference(qkv):
             return wmsa_forward(qkv, m.pad_kv(qkv), m.rpb_hw(), m.num_heads, self.shift_size, m.scale, self.window_size)
         if m.attn_drop.p > 0 and self.training:
             raise NotImplementedError("attn_drop_rate > 0 in training")
@@ -186,14 +178,13 @@ class ShiftWindowMSA(nn.Module):
 
     def forward(self, x):
         """x [B,H,W,C] (after norm1) -> [B,H,W,C] (DropPath in training)."""
-        from .segnet import _linear
         m = self.w_msa
         B, H, W, C = x.shape
         x2 = x.reshape(-1, C)
-        qkv = (_linear(x2.contiguous(), m.qkv) if _gpu_inference(x) else m.qkv(x2)).view(B, H, W, 3 * C)
+        qkv = (linear(x2.contiguous(), m.qkv) if gpu_inference(x) else m.qkv(x2)).view(B, H, W, 3 * C)
         o = self.attend(qkv).reshape(-1, C)
-        o = _linear(o.contiguous(), m.proj) if _gpu_inference(x) else m.proj(o)
-        return _drop_path(m.proj_drop(o.view(B, H, W, C)), self.drop_path_rate, self.training)
+        o = linear(o.contiguous(), m.proj) if gpu_inference(x) else m.proj(o)
+        return drop_path(m.proj_drop(o.view(B, H, W, C)), self.drop_path_rate, self.training)
 
 
 class FFN(nn.Module):
@@ -207,12 +198,11 @@ class FFN(nn.Module):
 
     def forward(self, x):
         """The branch only (the caller adds the identity): [B,H,W,C] -> [B,H,W,C]."""
-        from .segnet import _linear
         fc1, fc2 = self.layers[0][0], self.layers[1]
-        if _gpu_inference(x):
+        if gpu_inference(x):
             x2 = x.reshape(-1, x.shape[-1]).contiguous()
-            return _linear(_linear(x2, fc1, gelu=True), fc2).view(x.shape)
-        return _drop_path(self.layers(x), self.drop_path_rate, self.training)
+            return linear(linear(x2, fc1, gelu=True), fc2).view(x.shape)
+        return drop_path(self.layers(x), self.drop_path_rate, self.training)
 
 
 class SwinBlock(nn.Module):
@@ -229,7 +219,7 @@ class SwinBlock(nn.Module):
 
     def forward(self, x, y=None, next_norm=None):
         """x: residual stream [B,H,W,C]; y = norm1(x) if the caller has it.  Returns (x', next_norm(x') or None)."""
-        if _gpu_inference(x):
+        if gpu_inference(x):
             # LayerNorm and residual adds on the fused kernels (x is updated in place: the caller hands over a fresh tensor)
             if y is None:
                 y = fused.layer_norm(x, self.norm1)
@@ -258,41 +248,47 @@ class PatchMerging(nn.Module):
             x = F.pad(x, (0, 0, 0, W % 2, 0, H % 2))
         Ho, Wo = x.shape[1] // 2, x.shape[2] // 2
         x = x.reshape(B, Ho, 2, Wo, 2, C).permute(0, 1, 3, 5, 2, 4).reshape(B, Ho, Wo, 4 * C)
-        if _gpu_inference(x):
-            from .segnet import _linear
+        if gpu_inference(x):
             if self.norm is not None:
                 # the LayerNorm kernel takes rows of up to 1024 channels; the 2048-wide rows of Swin-B's last merge take the
                 # framework's LayerNorm (one launch per forward)
                 x = fused.layer_norm(x, self.norm) if 4 * C <= 1024 else F.layer_norm(x, (4 * C,), self.norm.weight, self.norm.bias, self.norm.eps)
-            return _linear(x.reshape(-1, 4 * C), self.reduction).view(B, Ho, Wo, -1)
+            return linear(x.reshape(-1, 4 * C), self.reduction).view(B, Ho, Wo, -1)
         if self.norm is not None:
             x = self.norm(x)
         return self.reduction(x)
 
 
 class PatchEmbed(nn.Module):
-    """embed.py:83-204: 'corner' adaptive padding, a kernel = stride convolution (the framework's convolution), LayerNorm."""
+    """embed.py:83-204 with kernel = stride = patch_size: 'corner' adaptive padding (bottom / right), the framework's convolution,
+    optional LayerNorm.  Swin calls the module; vit.py (same parameters and keys) calls project() and normalises its own [B,N,C] layout."""
 
-    def __init__(self, in_channels, embed_dims, patch_size, norm=True):
+    def __init__(self, in_channels, embed_dims, patch_size, norm=True, norm_eps=1e-5):
         super().__init__()
         self.patch_size = patch_size
         self.projection = nn.Conv2d(in_channels, embed_dims, patch_size, patch_size)
-        self.norm = nn.LayerNorm(embed_dims) if norm else None
+        self.norm = nn.LayerNorm(embed_dims, eps=norm_eps) if norm else None
 
     def takes_codes(self, grid_u8):
         return False                                   # SegNet.labels_u8 renders occupancy codes to an image first
 
-    def forward(self, x):
-        """x [B,3,H,W] -> tokens [B,H/4,W/4,C] (NHWC)."""
+    def project(self, x):
+        """x [B,3,H,W], or the u8 occupancy codes [B,H,W] it would be rendered from -> the projection [B,C,h,w], before the norm."""
+        if x.dtype == torch.uint8:
+            x = fused.grid_to_image(x, IMG_MEAN, IMG_STD, self.projection.weight.dtype)
         p = self.patch_size
         H, W = x.shape[-2:]
         ph, pw = (-H) % p, (-W) % p
         if ph or pw:
             x = F.pad(x, [0, pw, 0, ph])
-        x = self.projection(x).permute(0, 2, 3, 1)
+        return self.projection(x)
+
+    def forward(self, x):
+        """-> tokens [B,H/4,W/4,C] (NHWC)."""
+        x = self.project(x).permute(0, 2, 3, 1)
         if self.norm is None:
             return x
-        return fused.layer_norm(x, self.norm) if _gpu_inference(x) else self.norm(x)
+        return fused.layer_norm(x, self.norm) if gpu_inference(x) else self.norm(x)
 
 
 class SwinBlockSequence(nn.Module):
@@ -314,7 +310,7 @@ class SwinBlockSequence(nn.Module):
 
     def forward(self, x, out_norm=None):
         """Returns (next level's input, out_norm(x) or None)."""
-        if _gpu_inference(x):
+        if gpu_inference(x):
             x = x.contiguous().clone()                 # the fused kernels update the stream in place
         y = None
         n = len(self.blocks)
@@ -378,9 +374,6 @@ class SwinTransformer(nn.Module):
             self.load_state_dict(sd, strict=False)
 
     def forward(self, x):
-        if x.dtype == torch.uint8:
-            from .segnet import IMG_MEAN, IMG_STD
-            x = fused.grid_to_image(x, IMG_MEAN, IMG_STD, self.patch_embed.projection.weight.dtype)
         x = self.drop_after_pos(self.patch_embed(x))
         outs = [None] * len(self.out_indices)
         for i, stage in enumerate(self.stages):

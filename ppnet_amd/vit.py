@@ -5,7 +5,7 @@ constructor arguments and state-dict layout (`patch_embed.{projection,norm}`, `c
 
 Two forms of the same arithmetic:
 * GPU inference (CUDA tensors, no autograd): the qkv / out / MLP projections on the build's GEMMs where their gates pass
-  (segnet._linear, bias and GELU in the float32 epilogue; each branch joins the residual stream in one add), the global attention
+  (dense.linear, bias and GELU in the float32 epilogue; each branch joins the residual stream in one add), the global attention
   kernel ppn_mhsa_fwd between in_proj and out_proj.  The LayerNorm kernels take widths up to 512 and 1024, not ViT-B's 768: those
   rows take the framework's LayerNorm (fused.layer_norm_any_width); the patch embedding stays on the framework's convolution.
 * everything else (CPU, grad-enabled training on the GPU): nn.MultiheadAttention itself, with dropout, attention dropout and
@@ -20,7 +20,8 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import fused
-from .swin import FFN
+from .dense import drop_path, gpu_inference, linear
+from .swin import FFN, PatchEmbed
 
 HEAD_DIM = 64
 
@@ -28,15 +29,6 @@ HEAD_DIM = 64
 CALLS = {"kernel": 0}
 # Measurement hook like swin.TIMING: a list here makes every kernel launch record (start event, end event, B, N, heads, element size).
 TIMING = None
-
-
-def _drop_path(x, rate, training):
-    from .segnet import drop_path
-    return drop_path(x, rate, training)
-
-
-def _gpu_inference(x):
-    return x.is_cuda and not torch.is_grad_enabled()
 
 
 def mhsa_forward(qkv, heads, scale):
@@ -69,7 +61,7 @@ def mhsa_forward(qkv, heads, scale):
 
 
 class _Proj:
-    """in_proj_weight / in_proj_bias of an nn.MultiheadAttention seen as a Linear (what segnet._linear takes)."""
+    """in_proj_weight / in_proj_bias of an nn.MultiheadAttention seen as a Linear (what dense.linear takes)."""
 
     def __init__(self, mha):
         self.m = mha
@@ -95,13 +87,12 @@ class MultiheadAttention(nn.Module):
     def forward(self, x, identity):
         """x [B,N,C] (after ln1) -> identity + the attention branch (torch composition)."""
         out = self.attn(x.transpose(0, 1), x.transpose(0, 1), x.transpose(0, 1), need_weights=False)[0].transpose(0, 1)
-        return identity + _drop_path(self.proj_drop(out), self.drop_path_rate, self.training)
+        return identity + drop_path(self.proj_drop(out), self.drop_path_rate, self.training)
 
     def attend_gpu(self, y):
         """GPU inference: attention(in_proj(y)) for y [B,N,C] (before out_proj), on the build's GEMM and ppn_mhsa_fwd."""
-        from .segnet import _linear
         B, N, C = y.shape
-        qkv = _linear(y.reshape(-1, C).contiguous(), self._in_proj).view(B, N, 3 * C)
+        qkv = linear(y.reshape(-1, C).contiguous(), self._in_proj).view(B, N, 3 * C)
         return mhsa_forward(qkv, self.num_heads, (C // self.num_heads) ** -0.5)
 
 
@@ -122,48 +113,20 @@ class TransformerEncoderLayer(nn.Module):
 
     def forward(self, x, y=None, next_norm=None):
         """x: residual stream [B,N,C]; y = ln1(x) if the caller has it.  Returns (x', next_norm(x') or None)."""
-        if _gpu_inference(x):
+        if gpu_inference(x):
             # x is updated in place (the caller hands over a fresh tensor).  out_proj and fc2 run with their bias in the GEMM's
             # float32 epilogue, and each branch joins the stream in one add: the stream is rounded once per sub-layer
-            from .segnet import _linear
             B, N, C = x.shape
             x2 = x.view(-1, C)
             if y is None:
                 y = fused.layer_norm_any_width(x, self.ln1)
-            x2.add_(_linear(self.attn.attend_gpu(y).view(-1, C), self.attn.attn.out_proj))
-            h = _linear(fused.layer_norm_any_width(x, self.ln2).view(-1, C), self.ffn.layers[0][0], gelu=True)
-            x2.add_(_linear(h, self.ffn.layers[1]))
+            x2.add_(linear(self.attn.attend_gpu(y).view(-1, C), self.attn.attn.out_proj))
+            h = linear(fused.layer_norm_any_width(x, self.ln2).view(-1, C), self.ffn.layers[0][0], gelu=True)
+            x2.add_(linear(h, self.ffn.layers[1]))
             return x, (fused.layer_norm_any_width(x, next_norm) if next_norm is not None else None)
         x = self.attn(self.ln1(x), identity=x)
         x = x + self.ffn(self.ln2(x))
         return x, (next_norm(x) if next_norm is not None else None)
-
-
-class PatchEmbed(nn.Module):
-    """embed.py:83-204 with kernel = stride = patch_size and 'corner' adaptive padding (bottom / right), the framework's convolution,
-    optional LayerNorm.  forward -> tokens [B,N,C] and the token grid (h, w)."""
-
-    def __init__(self, in_channels, embed_dims, patch_size, norm_eps=None):
-        super().__init__()
-        self.patch_size = patch_size
-        self.projection = nn.Conv2d(in_channels, embed_dims, patch_size, patch_size)
-        self.norm = nn.LayerNorm(embed_dims, eps=norm_eps) if norm_eps is not None else None
-
-    def takes_codes(self, grid_u8):
-        return False                                   # SegNet.labels_u8 renders occupancy codes to an image first
-
-    def forward(self, x):
-        p = self.patch_size
-        H, W = x.shape[-2:]
-        ph, pw = (-H) % p, (-W) % p
-        if ph or pw:
-            x = F.pad(x, [0, pw, 0, ph])
-        x = self.projection(x)
-        hw = (x.shape[2], x.shape[3])
-        x = x.flatten(2).transpose(1, 2)
-        if self.norm is not None:
-            x = fused.layer_norm_any_width(x, self.norm) if _gpu_inference(x) else self.norm(x)
-        return x, hw
 
 
 def resize_pos_embed(pos_embed, input_shape, pos_shape, mode):
@@ -205,7 +168,7 @@ class VisionTransformer(nn.Module):
         eps = float(norm_cfg.get("eps", 1e-5))
         self.img_size, self.patch_size, self.interpolate_mode = img_size, patch_size, interpolate_mode
         self.norm_eval, self.pretrained = norm_eval, pretrained
-        self.patch_embed = PatchEmbed(in_channels, embed_dims, patch_size, eps if patch_norm else None)
+        self.patch_embed = PatchEmbed(in_channels, embed_dims, patch_size, patch_norm, norm_eps=eps)
         num_patches = (img_size[0] // patch_size) * (img_size[1] // patch_size)
         self.with_cls_token = with_cls_token
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dims))
@@ -279,7 +242,7 @@ class VisionTransformer(nn.Module):
         ph, pw = self.img_size[0] // self.patch_size, self.img_size[1] // self.patch_size
         if resize and pos.shape[1] != ph * pw + 1:
             raise ValueError(f"Unexpected shape of pos_embed, got {tuple(pos.shape)}.")
-        if _gpu_inference(x):
+        if gpu_inference(x):
             # computed once per (parameter, grid, dtype) and kept: resized in float32, then rounded to x's dtype
             cache = self.__dict__.get("_pos")
             if cache is None:
@@ -289,13 +252,15 @@ class VisionTransformer(nn.Module):
         return (resize_pos_embed(pos, hw, (ph, pw), self.interpolate_mode) if resize else pos).to(x.dtype)
 
     def forward(self, x):
-        if x.dtype == torch.uint8:
-            from .segnet import IMG_MEAN, IMG_STD
-            x = fused.grid_to_image(x, IMG_MEAN, IMG_STD, self.patch_embed.projection.weight.dtype)
         B = x.shape[0]
-        x, hw = self.patch_embed(x)
+        pe = self.patch_embed                          # swin.PatchEmbed's projection; the [B,N,C] tokens and their LayerNorm here
+        x = pe.project(x)
+        hw = (x.shape[2], x.shape[3])
+        x = x.flatten(2).transpose(1, 2)
+        if pe.norm is not None:
+            x = fused.layer_norm_any_width(x, pe.norm) if gpu_inference(x) else pe.norm(x)
         pos = self._grid_pos(hw, x)
-        gpu = _gpu_inference(x)
+        gpu = gpu_inference(x)
         if self.with_cls_token:
             x = torch.cat((self.cls_token.to(x.dtype).expand(B, -1, -1), x), dim=1) + pos
         else:
