@@ -66,8 +66,8 @@ extern "C" {
  * sizes, so a caller built against another header would link and pass, say, a batch size where a workspace pointer is expected.
  * Bumped whenever an entry point's argument list changes or an entry point is removed: 100 = rounds 1-3; 101 = round 4
  * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5; 106 = ppn_swin_wmsa_fwd; 107 = ppn_upsample2x_concat_nhwc;
- * 108 = ppn_mhsa_fwd. */
-#define PPN_ABI_VERSION 108
+ * 108 = ppn_mhsa_fwd; 109 = ppn_mhsa_bwd, ppn_mhsa_bwd_workspace. */
+#define PPN_ABI_VERSION 109
 int         ppn_version(void);
 const char* ppn_error_string(int code);
 int         ppn_last_hip_error(void);   /* hipError_t of the most recent PPN_E_HIP on this thread */
@@ -294,6 +294,21 @@ int ppn_swin_wmsa_fwd(const void* qkv, const void* pad_kv, const float* rpb, voi
  * accumulation, the output rounded once). */
 int ppn_mhsa_fwd(const void* qkv, void* out, int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, int32_t dtype,
                  void* stream);
+
+/* Backward of ppn_mhsa_fwd: with P = softmax(scale q k^T) per (batch, head), dV = P^T dO, dS = P o (dO V^T - rowsum(dO o O)),
+ * dQ = scale dS K, dK = scale dS^T Q.  qkv and out as in the forward (out is what ppn_mhsa_fwd returned for this qkv), dout
+ * [B][N][heads][head_dim]; dqkv has qkv's layout and is fully WRITTEN (all three thirds of every row), never accumulated into.
+ * Three passes (per-query softmax statistics and rowsum(dO o O) into the workspace; dK / dV per key block; dQ per query block):
+ * P is recomputed, nothing of size N x N is stored, every output element has one writer and no atomics are used, so the
+ * gradients are bitwise reproducible.  workspace: ppn_mhsa_bwd_workspace(B, N, heads) floats (2 * B * heads * N), 16-byte
+ * aligned; workspace_floats is what the caller allocated and is checked.  head_dim must be 64 (else PPN_E_UNSUPPORTED); any
+ * N >= 1.  NULL pointers, B / N / heads <= 0, a non-finite or non-positive scale, a dtype other than 0 / 1, buffers not 16-byte
+ * aligned, a workspace that is too small and launches of 2^31 work-items or more return PPN_E_INVALID before any HIP call.
+ * dtype 0 = float32 (VALU), 1 = bfloat16 (matrix cores: float32 softmax arithmetic and accumulation, P and dS rounded to
+ * bfloat16 once each as operands, dqkv rounded once). */
+int64_t ppn_mhsa_bwd_workspace(int32_t B, int32_t N, int32_t heads);      /* floats; < 0: invalid shape */
+int ppn_mhsa_bwd(const void* qkv, const void* out, const void* dout, void* dqkv, float* workspace, int64_t workspace_floats,
+                 int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, int32_t dtype, void* stream);
 
 /* Backward of ppn_na2d_fwd (the gradient NATTEN's natten2dqkrpb / natten2dav backward kernels compute; first brick of the
  * training step, GenNet/train.py:93-147, SegNet/mmseg/apis/train.py:67-167).  qkv [B][H][W][3][heads][32] and rpb as in the

@@ -388,6 +388,28 @@ int ppn_mhsa_fwd(const void* qkv, void* out, int32_t B, int32_t N, int32_t heads
     return PPN_OK;
 }
 
+int64_t ppn_mhsa_bwd_workspace(int32_t B, int32_t N, int32_t heads) {
+    if (B <= 0 || N <= 0 || heads <= 0) return -1;
+    if ((long long)B * heads >= (1LL << 40) / N) return -1;                                // statistics of fewer than 2^40 queries
+    return ppn::mhsa_bwd_workspace_floats(B, N, heads);
+}
+
+int ppn_mhsa_bwd(const void* qkv, const void* out, const void* dout, void* dqkv, float* workspace, int64_t workspace_floats,
+                 int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, int32_t dtype, void* stream) {
+    if (!qkv || !out || !dout || !dqkv || !workspace || B <= 0 || N <= 0 || heads <= 0 || head_dim <= 0 || (dtype != 0 && dtype != 1))
+        return PPN_E_INVALID;
+    if (!(scale > 0.0f) || scale > 3.0e38f) return PPN_E_INVALID;                        // NaN, inf, zero, negative
+    if (head_dim != 64) return PPN_E_UNSUPPORTED;
+    if ((((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv | (uintptr_t)workspace) & 15) != 0) return PPN_E_INVALID;
+    const long long block = dtype == 0 ? 64 : 128, threads = dtype == 0 ? 128 : 256;       // rows / work-items per workgroup, every pass
+    if ((long long)B * heads * ((N + block - 1) / block) * threads >= 0x7fffffffLL) return PPN_E_INVALID;
+    const int64_t need = ppn_mhsa_bwd_workspace(B, N, heads);
+    if (need < 0 || workspace_floats < need) return PPN_E_INVALID;
+    const int e = ppn::mhsa_bwd_launch(qkv, out, dout, dqkv, workspace, B, N, heads, scale, dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_residual_layernorm(const void* x, const void* a, const void* gamma, const void* w, const void* b, void* x_out,
                            void* y_out, int64_t rows, int32_t C, float eps, int32_t dtype, void* stream) {
     return ppn_residual_layernorm_padded(x, a, gamma, w, b, x_out, y_out, rows, C, eps, dtype, 0, 0, 0, 0, stream);

@@ -141,6 +141,9 @@ int assemble_paths_launch(const double* wp, const int32_t* wp_n, const uint8_t* 
 int plan_collision_launch(const double* full, const int32_t* counts, const void* obstacles, int obs_f64, const int32_t* n_obs, int B, int M, int S,
                           float clearance, float bound, uint8_t* collision, hipStream_t stream);
 int mhsa_launch(const void* qkv, void* out, int B, int N, int heads, float scale, int dtype, hipStream_t stream);
+long long mhsa_bwd_workspace_floats(int B, int N, int heads);
+int mhsa_bwd_launch(const void* qkv, const void* out, const void* dout, void* dqkv, float* workspace, int B, int N, int heads, float scale, int dtype,
+                    hipStream_t stream);
 int swin_wmsa_launch(const void* qkv, const void* pad_kv, const float* rpb, void* out, int B, int H, int W, int heads, int shift, float scale,
                      int dtype, hipStream_t stream);
 int na2d_dense7_launch(const void* qkv, const void* pad_kv, const float* rpb, void* out, int B, int H, int W, int Hr, int Wr, int heads, int dil,

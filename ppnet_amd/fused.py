@@ -1,8 +1,8 @@
 """Host side of the fused residual / LayerScale / LayerNorm kernel (ppn_residual_layernorm). GPU only.
 
 Inference runs the HIP kernels below.  When autograd is recording (a training step, ppnet_amd/train.py) the same functions
-compose differentiable torch ops instead — the fused kernels are forward-only; the one hand-written backward is the
-neighbourhood attention's (ppn_na2d_bwd)."""
+compose differentiable torch ops instead — the fused kernels are forward-only; the hand-written backwards are the two
+attentions': neighbourhood (ppn_na2d_bwd, na.na2d_autograd) and ViT's global one (ppn_mhsa_bwd, vit.mhsa_autograd)."""
 import ctypes
 
 import torch

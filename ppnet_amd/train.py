@@ -10,9 +10,10 @@ MMDistributedDataParallel = gradient all-reduce averaged over the ranks).
 
 What is native here: the training PAIRS come straight from the generator kernels on the device (stage A/B + ppn_label_masks:
 mask_space / mask_path / the rendered map — the reference re-reads them from image files, my_dataset.py:30-76), the
-neighbourhood attention's backward is the HIP kernel (ppn_na2d_bwd through na.na2d_autograd), and the gradient exchange is
-torch's DistributedDataParallel over RCCL with buckets sized for xGMI rings (few large all-reduces).  Every other op of the
-backward pass is a ROCm library call through autograd: the fused inference kernels are forward-only and step aside while
+neighbourhood attention's backward is the HIP kernel (ppn_na2d_bwd through na.na2d_autograd), so is the ViT backbone's global
+attention's (ppn_mhsa_bwd through vit.mhsa_autograd: no N x N tensor saved, bitwise-reproducible gradients), and the gradient
+exchange is torch's DistributedDataParallel over RCCL with buckets sized for xGMI rings (few large all-reduces).  Every other op
+of the backward pass is a ROCm library call through autograd: the fused inference kernels are forward-only and step aside while
 autograd is recording (fused.recording).
 """
 import torch
@@ -129,6 +130,8 @@ class _SegTrain(nn.Module):
         for i in getattr(bb, "out_indices", ()):
             if i not in bb.compute_indices:
                 getattr(bb, f"norm{i}").requires_grad_(False)
+        if getattr(bb, "with_cls_token", True) is False:
+            bb.cls_token.requires_grad_(False)                                 # ViT without its class token never reads the parameter
 
     def forward(self, img, labels):
         losses = self.net.forward_train(img, None, labels)

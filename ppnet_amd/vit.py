@@ -8,8 +8,12 @@ Two forms of the same arithmetic:
   (dense.linear, bias and GELU in the float32 epilogue; each branch joins the residual stream in one add), the global attention
   kernel ppn_mhsa_fwd between in_proj and out_proj.  The LayerNorm kernels take widths up to 512 and 1024, not ViT-B's 768: those
   rows take the framework's LayerNorm (fused.layer_norm_any_width); the patch embedding stays on the framework's convolution.
-* everything else (CPU, grad-enabled training on the GPU): nn.MultiheadAttention itself, with dropout, attention dropout and
-  drop path as the reference applies them.
+* GPU training (autograd recording, float32 / bfloat16 tokens, head dim 64, attention dropout inactive): in_proj and out_proj
+  on the library's GEMMs (differentiable, as every dense op of the training step), between them mhsa_autograd — ppn_mhsa_fwd
+  forward and ppn_mhsa_bwd (csrc/mhsa_bwd.hip) backward: P is recomputed from qkv and per-query statistics, so a layer saves qkv
+  and out and nothing of size N x N, and the gradients are bitwise reproducible (no atomics).  Dropout and drop path as the
+  reference applies them.
+* everything else (CPU, other head dims, active attention dropout): nn.MultiheadAttention itself.
 """
 import ctypes
 import math
@@ -25,8 +29,8 @@ from .swin import FFN, PatchEmbed
 
 HEAD_DIM = 64
 
-# Launch counter (tests / tools): how many attentions ran on the HIP kernel.
-CALLS = {"kernel": 0}
+# Launch counters (tests / tools): how many attentions ran on the HIP forward kernel, how many backwards on ppn_mhsa_bwd.
+CALLS = {"kernel": 0, "bwd_kernel": 0}
 # Measurement hook like swin.TIMING: a list here makes every kernel launch record (start event, end event, B, N, heads, element size).
 TIMING = None
 
@@ -60,6 +64,43 @@ def mhsa_forward(qkv, heads, scale):
     return out
 
 
+class _MHSAFunction(torch.autograd.Function):
+    """qkv [B,N,3*heads*64] -> [B,N,heads*64] on ppn_mhsa_fwd; backward on ppn_mhsa_bwd.  Saves qkv and out, nothing else."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, scale):
+        qkv = qkv.detach().contiguous()
+        out = mhsa_forward(qkv, heads, scale)
+        ctx.save_for_backward(qkv, out)
+        ctx.meta = (heads, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out = ctx.saved_tensors
+        heads, scale = ctx.meta
+        B, N, _ = qkv.shape
+        dout = dout.to(qkv.dtype).contiguous()
+        dqkv = torch.empty_like(qkv)
+        need = L.lib.ppn_mhsa_bwd_workspace(B, N, heads)                  # per-query softmax statistic and rowsum(dO o O); P is recomputed
+        if need < 0:
+            raise ValueError(f"ppn_mhsa_bwd: shape {(B, N, heads)} is outside the kernel")
+        ws = torch.empty(need, dtype=torch.float32, device=qkv.device)
+        dtype = {torch.float32: 0, torch.bfloat16: 1}[qkv.dtype]
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        with torch.cuda.device(qkv.device):
+            rc = L.lib.ppn_mhsa_bwd(p(qkv), p(out), p(dout), p(dqkv), p(ws), need, B, N, heads, HEAD_DIM, float(scale), dtype,
+                                    ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream))
+        L.check(rc, "ppn_mhsa_bwd")
+        CALLS["bwd_kernel"] += 1
+        return dqkv, None, None
+
+
+def mhsa_autograd(qkv, heads, scale):
+    """Differentiable global attention on qkv [B,N,3*heads*64] CUDA (float32 / bfloat16): ppn_mhsa_fwd, and ppn_mhsa_bwd in backward."""
+    return _MHSAFunction.apply(qkv, heads, scale)
+
+
 class _Proj:
     """in_proj_weight / in_proj_bias of an nn.MultiheadAttention seen as a Linear (what dense.linear takes)."""
 
@@ -85,8 +126,16 @@ class MultiheadAttention(nn.Module):
         self.__dict__["_in_proj"] = _Proj(self.attn)
 
     def forward(self, x, identity):
-        """x [B,N,C] (after ln1) -> identity + the attention branch (torch composition)."""
-        out = self.attn(x.transpose(0, 1), x.transpose(0, 1), x.transpose(0, 1), need_weights=False)[0].transpose(0, 1)
+        """x [B,N,C] (after ln1) -> identity + the attention branch.  Training on the GPU: library GEMMs around mhsa_autograd;
+        every other case the torch composition."""
+        a = self.attn
+        if (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and self.embed_dims == self.num_heads * HEAD_DIM
+                and (a.dropout == 0.0 or not self.training)
+                and fused.recording(x, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias)):
+            qkv = F.linear(x, a.in_proj_weight, a.in_proj_bias)
+            out = F.linear(mhsa_autograd(qkv, self.num_heads, HEAD_DIM ** -0.5), a.out_proj.weight, a.out_proj.bias)
+        else:
+            out = a(x.transpose(0, 1), x.transpose(0, 1), x.transpose(0, 1), need_weights=False)[0].transpose(0, 1)
         return identity + drop_path(self.proj_drop(out), self.drop_path_rate, self.training)
 
     def attend_gpu(self, y):
