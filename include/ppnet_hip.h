@@ -66,8 +66,8 @@ extern "C" {
  * sizes, so a caller built against another header would link and pass, say, a batch size where a workspace pointer is expected.
  * Bumped whenever an entry point's argument list changes or an entry point is removed: 100 = rounds 1-3; 101 = round 4
  * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5; 106 = ppn_swin_wmsa_fwd; 107 = ppn_upsample2x_concat_nhwc;
- * 108 = ppn_mhsa_fwd; 109 = ppn_mhsa_bwd, ppn_mhsa_bwd_workspace. */
-#define PPN_ABI_VERSION 109
+ * 108 = ppn_mhsa_fwd; 109 = ppn_mhsa_bwd, ppn_mhsa_bwd_workspace; 110 = ppn_swin_wmsa_bwd, ppn_swin_wmsa_bwd_workspace. */
+#define PPN_ABI_VERSION 110
 int         ppn_version(void);
 const char* ppn_error_string(int code);
 int         ppn_last_hip_error(void);   /* hipError_t of the most recent PPN_E_HIP on this thread */
@@ -283,6 +283,30 @@ int ppn_na2d_fwd_vpad(const void* qkv, const void* pad_kv, const float* rpb, voi
  * dtype 0 = float32, 1 = bfloat16 (float32 accumulation, matrix cores). */
 int ppn_swin_wmsa_fwd(const void* qkv, const void* pad_kv, const float* rpb, void* out, int32_t B, int32_t H, int32_t W,
                       int32_t heads, int32_t window, int32_t shift, float scale, int32_t dtype, void* stream);
+
+/* Backward of ppn_swin_wmsa_fwd, in its layouts and index arithmetic.  Per (image, window, head), over the 49 slots, with the
+ * logit L_ij = scale q_i . k_j + rpb[h][rel(i, j)] + mask_ij (the -100 region mask of a shifted layer, not -inf):
+ *   P = softmax_j(L);  dP_ij = dO_i . v_j;  delta_i = sum_j P_ij dP_ij (= rowsum(dO o O): the forward's output is not an input);
+ *   dS_ij = P_ij (dP_ij - delta_i);  dV_j = sum_i P_ij dO_i;  dQ_i = scale sum_j dS_ij k_j;  dK_j = scale sum_i dS_ij q_i.
+ * dout [B][H][W][heads*32] (real tokens; a padded query has dO = 0 and contributes nothing).  Outputs, all fully WRITTEN and never
+ * accumulated into: dqkv in qkv's layout and dtype; dpad_kv [3][heads][32] float32 — a padded key / value slot's dK / dV belongs
+ * to pad_kv (the qkv bias): its k and v thirds are the sums of dK / dV over all padded positions of all images, its q third is
+ * exactly 0, and all of it is 0 when H and W are multiples of 7; drpb [heads][13][13] float32 with drpb[h][dy + 6][dx + 6] = the
+ * sum of dS_ij over images, windows and slot pairs with query-minus-key offset (dy, dx), padded keys included (the mask does not
+ * change it).  One (window, head) is computed end to end by one wave (bfloat16) or workgroup (float32), so dqkv has one writer per
+ * element; drpb and dpad_kv are summed per workgroup over the windows it walks and then over the workgroups by a second kernel, in
+ * a fixed order and without atomics: the gradients are bitwise reproducible.  workspace: ppn_swin_wmsa_bwd_workspace(...) floats
+ * (the per-workgroup partial sums: the size depends on the current device), 16-byte aligned; workspace_floats is what the caller
+ * allocated and is checked.  NULL pointers, B / H / W / heads <= 0, heads > 65535, a non-finite or non-positive scale, a dtype
+ * other than 0 / 1, any buffer not 16-byte aligned, a workspace that is too small and B * windows >= 2^31 return PPN_E_INVALID,
+ * window != 7 or shift not in {0, 3} PPN_E_UNSUPPORTED, before any HIP launch (the workspace check comes last: its size is the one
+ * thing that asks the runtime, for the device's compute-unit count).  dtype 0 = float32 (VALU), 1 = bfloat16 (matrix
+ * cores: float32 softmax arithmetic and accumulation, P and dS rounded to bfloat16 once each as operands, dqkv rounded once). */
+int64_t ppn_swin_wmsa_bwd_workspace(int32_t B, int32_t H, int32_t W, int32_t heads);     /* floats; < 0: invalid shape */
+int ppn_swin_wmsa_bwd(const void* qkv, const void* pad_kv, const float* rpb, const void* dout,
+                      void* dqkv, float* dpad_kv, float* drpb, float* workspace, int64_t workspace_floats,
+                      int32_t B, int32_t H, int32_t W, int32_t heads, int32_t window, int32_t shift,
+                      float scale, int32_t dtype, void* stream);
 
 /* Global multi-head self-attention, forward (the body of nn.MultiheadAttention between in_proj and out_proj, which mmseg's
  * VisionTransformer calls through mmcv's MultiheadAttention, SegNet/mmseg/backbones/vit.py:63-70,92-95):

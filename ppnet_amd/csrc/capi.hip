@@ -375,6 +375,33 @@ int ppn_swin_wmsa_fwd(const void* qkv, const void* pad_kv, const float* rpb, voi
     return PPN_OK;
 }
 
+int64_t ppn_swin_wmsa_bwd_workspace(int32_t B, int32_t H, int32_t W, int32_t heads) {
+    if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || heads > 65535) return -1;
+    return ppn::swin_wmsa_bwd_workspace_floats(heads);
+}
+
+int ppn_swin_wmsa_bwd(const void* qkv, const void* pad_kv, const float* rpb, const void* dout, void* dqkv, float* dpad_kv, float* drpb,
+                      float* workspace, int64_t workspace_floats, int32_t B, int32_t H, int32_t W, int32_t heads, int32_t window, int32_t shift,
+                      float scale, int32_t dtype, void* stream) {
+    if (!qkv || !pad_kv || !rpb || !dout || !dqkv || !dpad_kv || !drpb || !workspace) return PPN_E_INVALID;
+    if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || heads > 65535 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;
+    if (!(scale > 0.0f) || scale > 3.0e38f) return PPN_E_INVALID;                        // NaN, inf, zero, negative
+    if (window != 7 || (shift != 0 && shift != 3)) return PPN_E_UNSUPPORTED;             // Swin-B's window; shift = window // 2
+    if ((((uintptr_t)qkv | (uintptr_t)pad_kv | (uintptr_t)rpb | (uintptr_t)dout | (uintptr_t)dqkv | (uintptr_t)dpad_kv | (uintptr_t)drpb |
+          (uintptr_t)workspace) & 15) != 0)
+        return PPN_E_INVALID;
+    // window numbers are 32-bit (token offsets 64-bit); in steps, each within 64 bits: H W < 2^31, so windows per image < 2^31, then B x that
+    if ((long long)H * W >= 0x7fffffffLL) return PPN_E_INVALID;
+    const long long per_image = ((H + 6LL) / 7) * ((W + 6LL) / 7);
+    if (per_image >= 0x7fffffffLL || (long long)B * per_image >= 0x7fffffffLL) return PPN_E_INVALID;
+    const int64_t need = ppn_swin_wmsa_bwd_workspace(B, H, W, heads);                    // per device: the one check that asks the runtime
+    if (need < 0 || workspace_floats < need) return PPN_E_INVALID;
+    const int e = ppn::swin_wmsa_bwd_launch(qkv, pad_kv, rpb, dout, dqkv, dpad_kv, drpb, workspace, B, H, W, heads, shift, scale, dtype,
+                                            (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_mhsa_fwd(const void* qkv, void* out, int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, int32_t dtype,
                  void* stream) {
     if (!qkv || !out || B <= 0 || N <= 0 || heads <= 0 || head_dim <= 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;

@@ -146,6 +146,9 @@ int mhsa_bwd_launch(const void* qkv, const void* out, const void* dout, void* dq
                     hipStream_t stream);
 int swin_wmsa_launch(const void* qkv, const void* pad_kv, const float* rpb, void* out, int B, int H, int W, int heads, int shift, float scale,
                      int dtype, hipStream_t stream);
+long long swin_wmsa_bwd_workspace_floats(int heads);
+int swin_wmsa_bwd_launch(const void* qkv, const void* pad_kv, const float* rpb, const void* dout, void* dqkv, float* dpad_kv, float* drpb,
+                         float* workspace, int B, int H, int W, int heads, int shift, float scale, int dtype, hipStream_t stream);
 int na2d_dense7_launch(const void* qkv, const void* pad_kv, const float* rpb, void* out, int B, int H, int W, int Hr, int Wr, int heads, int dil,
                        float scale, hipStream_t stream);
 int gennet_dec_final_launch(const void* x, const void* wt, const float* bias, float slope, const float* w1, float bias1, void* y, int B, int H, int W,

@@ -2,7 +2,8 @@
 
 Inference runs the HIP kernels below.  When autograd is recording (a training step, ppnet_amd/train.py) the same functions
 compose differentiable torch ops instead — the fused kernels are forward-only; the hand-written backwards are the two
-attentions': neighbourhood (ppn_na2d_bwd, na.na2d_autograd) and ViT's global one (ppn_mhsa_bwd, vit.mhsa_autograd)."""
+attentions': neighbourhood (ppn_na2d_bwd, na.na2d_autograd), ViT's global one (ppn_mhsa_bwd, vit.mhsa_autograd) and Swin's window one
+(ppn_swin_wmsa_bwd, swin.wmsa_autograd)."""
 import ctypes
 
 import torch

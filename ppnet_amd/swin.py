@@ -6,7 +6,11 @@ relative_position_bias_table,relative_position_index},norm2,ffn.layers.{0.0,1}}`
 Two forms of the same arithmetic:
 * GPU inference (CUDA tensors, no autograd): LayerNorm kernels, the build's GEMMs where their gates pass (dense.linear) and the
   fused (shifted-)window attention kernel ppn_swin_wmsa_fwd between the qkv and proj projections.
-* everything else (CPU, grad-enabled training on the GPU): a pure-torch composition of mmseg's ops (`window_attention`).
+* GPU training (CUDA tensors, autograd recording, head dim 32, window 7): library GEMMs for the qkv / proj Linears around
+  `wmsa_autograd`: ppn_swin_wmsa_fwd forward and ppn_swin_wmsa_bwd (csrc/swin_wmsa_bwd.hip) backward.  P is recomputed from qkv,
+  so a block saves qkv, the qkv bias and the bias table and nothing of size 49 x 49; the gradients of qkv, of the qkv bias (the
+  padded positions' k / v) and of the bias table are bitwise reproducible.
+* everything else (CPU, other head dims or windows): a pure-torch composition of mmseg's ops (`window_attention`).
 """
 import ctypes
 
@@ -23,6 +27,8 @@ HEAD_DIM = 32
 
 # Launch counter (tests / tools): how many window attentions ran on the HIP kernel and how many on the torch composition.
 CALLS = {"kernel": 0, "torch": 0}
+# The training path's launches (wmsa_autograd): forwards on ppn_swin_wmsa_fwd (not counted in CALLS), backwards on ppn_swin_wmsa_bwd.
+TRAIN_CALLS = {"fwd_kernel": 0, "bwd_kernel": 0}
 # Measurement hook like na.TIMING: a list here makes every kernel launch record (start event, end event, real tokens, channels,
 # element size).
 TIMING = None
@@ -95,6 +101,12 @@ def _relative_index(window, device=None):
 
 def wmsa_forward(qkv, pad_kv, rpb_hw, heads, shift, scale, window=WINDOW):
     """ppn_swin_wmsa_fwd: qkv [B,H,W,3C] CUDA (float32 / bfloat16), pad_kv [3C], rpb_hw [heads,13,13] float32 -> [B,H,W,C]."""
+    out = _wmsa_launch(qkv, pad_kv, rpb_hw, heads, shift, scale, window)
+    CALLS["kernel"] += 1
+    return out
+
+
+def _wmsa_launch(qkv, pad_kv, rpb_hw, heads, shift, scale, window=WINDOW):
     if not qkv.is_cuda:
         raise RuntimeError("ppnet_amd.swin: the window-attention kernel runs on the GPU only (no CPU fallback)")
     B, H, W, C3 = qkv.shape
@@ -118,11 +130,57 @@ def wmsa_forward(qkv, pad_kv, rpb_hw, heads, shift, scale, window=WINDOW):
                                      ctypes.c_void_p(out.data_ptr()), B, H, W, heads, window, shift, float(scale), dtype,
                                      ctypes.c_void_p(stream.cuda_stream))
     L.check(rc, "ppn_swin_wmsa_fwd")
-    CALLS["kernel"] += 1
     if ev is not None:
         ev[1].record()
         TIMING.append((ev[0], ev[1], B * H * W, C, qkv.element_size()))
     return out
+
+
+class _WMSAFunction(torch.autograd.Function):
+    """(qkv [B,H,W,3C], pad_kv [3C], table [(2w-1)^2, heads]) -> [B,H,W,C] on ppn_swin_wmsa_fwd; backward on ppn_swin_wmsa_bwd.
+    Saves qkv, pad_kv and the [heads,13,13] float32 table, nothing else."""
+
+    @staticmethod
+    def forward(ctx, qkv, pad_kv, table, heads, shift, scale):
+        qkv = qkv.detach().contiguous()
+        pad = pad_kv.detach().to(qkv.dtype).contiguous()
+        rpb_hw = bias_table_hw(table.detach().float(), heads).contiguous()
+        out = _wmsa_launch(qkv, pad, rpb_hw, heads, shift, scale)
+        TRAIN_CALLS["fwd_kernel"] += 1
+        ctx.save_for_backward(qkv, pad, rpb_hw)
+        ctx.meta = (heads, shift, scale, pad_kv.dtype, table.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, pad, rpb_hw = ctx.saved_tensors
+        heads, shift, scale, pad_dtype, table_dtype = ctx.meta
+        B, H, W, _ = qkv.shape
+        dout = dout.to(qkv.dtype).contiguous()
+        dqkv = torch.empty_like(qkv)
+        dpad = torch.empty(3 * heads * HEAD_DIM, dtype=torch.float32, device=qkv.device)
+        drpb = torch.empty(heads, 2 * WINDOW - 1, 2 * WINDOW - 1, dtype=torch.float32, device=qkv.device)
+        with torch.cuda.device(qkv.device):
+            need = L.lib.ppn_swin_wmsa_bwd_workspace(B, H, W, heads)      # the workgroups' partial sums of drpb and dpad_kv
+            if need < 0:
+                raise ValueError(f"ppn_swin_wmsa_bwd: shape {(B, H, W, heads)} is outside the kernel")
+            ws = torch.empty(need, dtype=torch.float32, device=qkv.device)
+            p = lambda t: ctypes.c_void_p(t.data_ptr())
+            rc = L.lib.ppn_swin_wmsa_bwd(p(qkv), p(pad), p(rpb_hw), p(dout), p(dqkv), p(dpad), p(drpb), p(ws), need, B, H, W, heads, WINDOW,
+                                         shift, float(scale), {torch.float32: 0, torch.bfloat16: 1}[qkv.dtype],
+                                         ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream))
+        L.check(rc, "ppn_swin_wmsa_bwd")
+        TRAIN_CALLS["bwd_kernel"] += 1
+        dtable = drpb.reshape(heads, -1).t().to(table_dtype) if ctx.needs_input_grad[2] else None     # the inverse of bias_table_hw
+        return dqkv, (dpad.to(pad_dtype) if ctx.needs_input_grad[1] else None), dtable, None, None, None
+
+
+def wmsa_autograd(qkv, pad_kv, table, heads, shift, scale):
+    """Differentiable window attention on qkv [B,H,W,3*heads*32] CUDA (float32 / bfloat16), pad_kv [3C] (the qkv bias), table
+    [(2w-1)^2, heads] (the parameter's layout): ppn_swin_wmsa_fwd, and ppn_swin_wmsa_bwd in backward (window 7, shift 0 or 3)."""
+    if not qkv.is_cuda:
+        raise RuntimeError("ppnet_amd.swin: the window-attention kernel runs on the GPU only (no CPU fallback)")
+    return _WMSAFunction.apply(qkv, pad_kv, table, heads, shift, scale)
 
 
 class WindowMSA(nn.Module):
@@ -167,14 +225,24 @@ class ShiftWindowMSA(nn.Module):
         self.drop_path_rate = float(drop_path_rate)
 
     def attend(self, qkv):
-        """Attention of qkv [B,H,W,3C] (before proj): the HIP kernel for GPU inference, the torch composition otherwise."""
+        """Attention of qkv [B,H,W,3C] (before proj): the HIP forward kernel for GPU inference, the forward and backward kernels
+        (wmsa_autograd) when autograd records on the GPU, the torch composition otherwise."""
         m = self.w_msa
         if gpu_inference(qkv):
             return wmsa_forward(qkv, m.pad_kv(qkv), m.rpb_hw(), m.num_heads, self.shift_size, m.scale, self.window_size)
         if m.attn_drop.p > 0 and self.training:
             raise NotImplementedError("attn_drop_rate > 0 in training")
+        if self.trains_on_kernel(qkv):
+            return wmsa_autograd(qkv, m.pad_kv(qkv), m.relative_position_bias_table, m.num_heads, self.shift_size, m.scale)
         return window_attention(qkv, m.pad_kv(qkv), m.relative_position_bias_table, m.num_heads, self.shift_size, m.scale,
                                 self.window_size)
+
+    def trains_on_kernel(self, qkv):
+        """Autograd records, on CUDA float32 / bfloat16 tensors, with the kernels' head dim, window and shifts."""
+        m = self.w_msa
+        return (qkv.is_cuda and qkv.dtype in (torch.float32, torch.bfloat16) and m.embed_dims == m.num_heads * HEAD_DIM
+                and self.window_size == WINDOW and self.shift_size in (0, WINDOW // 2)
+                and fused.recording(qkv, m.qkv.bias, m.relative_position_bias_table))
 
     def forward(self, x):
         """x [B,H,W,C] (after norm1) -> [B,H,W,C] (DropPath in training)."""
