@@ -66,8 +66,9 @@ extern "C" {
  * sizes, so a caller built against another header would link and pass, say, a batch size where a workspace pointer is expected.
  * Bumped whenever an entry point's argument list changes or an entry point is removed: 100 = rounds 1-3; 101 = round 4
  * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5; 106 = ppn_swin_wmsa_fwd; 107 = ppn_upsample2x_concat_nhwc;
- * 108 = ppn_mhsa_fwd; 109 = ppn_mhsa_bwd, ppn_mhsa_bwd_workspace; 110 = ppn_swin_wmsa_bwd, ppn_swin_wmsa_bwd_workspace. */
-#define PPN_ABI_VERSION 110
+ * 108 = ppn_mhsa_fwd; 109 = ppn_mhsa_bwd, ppn_mhsa_bwd_workspace; 110 = ppn_swin_wmsa_bwd, ppn_swin_wmsa_bwd_workspace;
+ * 111 = ppn_na2d_bwd_vpad, ppn_na2d_bwd_vpad_workspace. */
+#define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
 int         ppn_last_hip_error(void);   /* hipError_t of the most recent PPN_E_HIP on this thread */
@@ -345,6 +346,28 @@ int ppn_mhsa_bwd(const void* qkv, const void* out, const void* dout, void* dqkv,
 int64_t ppn_na2d_bwd_workspace(int32_t B, int32_t H, int32_t W, int32_t heads, int32_t dilation);   /* floats; < 0: invalid shape */
 int ppn_na2d_bwd(const void* qkv, const float* rpb, const void* dout, void* dqkv, float* drpb, float* workspace, int64_t workspace_floats,
                  int32_t B, int32_t H, int32_t W, int32_t heads, int32_t dilation, float scale, int32_t dtype, void* stream);
+
+/* Backward of ppn_na2d_fwd_vpad: ppn_na2d_bwd on the grid that the virtual padding defines, without building it.  H, W name the
+ * padded grid and Hr, Wr the real tokens, in ppn_na2d_fwd_vpad's argument order.  qkv [B][Hr][Wr][3][heads][32] (real tokens only);
+ * every position of the H x W grid outside Hr x Wr has k, v = pad_kv[3][heads][32] (in qkv's dtype; its q third is not read); only
+ * real tokens are queries; dout [B][Hr][Wr][heads*32].  Outputs, all fully WRITTEN and never accumulated into: dqkv in qkv's layout
+ * and dtype (real tokens only); drpb [heads][13][13] float32, padded keys included, as in the materialised form; dpad_kv
+ * [3][heads][32] float32 — its k third is the sum of dK over all padded positions of all images, its v third the sum of dV over the
+ * same positions, its q third exactly 0 (a padded query is cropped: dO = 0), and all of it exactly 0 when Hr == H and Wr == W.
+ * float32 arithmetic for both dtypes; the probabilities are recomputed in the key pass from 16 bytes of statistics per real query;
+ * all padded keys of a query's window share one k and one v, so their dK / dV are formed per query from two scalars (sum p, sum dS
+ * over those keys) and summed per workgroup in query order; a key's range of queries ends at the last real one (a padded query has
+ * no statistics); one writer per dqkv element, no atomics, fixed-order sums: the three outputs are bitwise reproducible.
+ * workspace: ppn_na2d_bwd_vpad_workspace(...) floats, 16-byte aligned = 4 * B * heads * Hr * Wr (statistics of the real queries)
+ * + 233 * heads * workgroups (169 drpb bins + 2 x 32 dpad_kv sums each), workgroups = B * dilation^2 * ceil(ceil(H / dilation) / 8)
+ * * ceil(ceil(W / dilation) / 8); workspace_floats is what the caller allocated and is checked.  NULL pointers, B / Hr / Wr / heads
+ * <= 0, Hr > H or Wr > W, H or W < 7 * dilation, heads > 65535, a non-finite or non-positive scale, a dtype other than 0 / 1, any
+ * buffer not 16-byte aligned, a workspace that is too small and 2^31 workgroups or more return PPN_E_INVALID before any HIP call
+ * (ppn_na2d_bwd_vpad_workspace returns < 0 for such a shape). */
+int64_t ppn_na2d_bwd_vpad_workspace(int32_t B, int32_t H, int32_t W, int32_t Hr, int32_t Wr, int32_t heads, int32_t dilation);
+int ppn_na2d_bwd_vpad(const void* qkv, const void* pad_kv, const float* rpb, const void* dout, void* dqkv, float* dpad_kv,
+                      float* drpb, float* workspace, int64_t workspace_floats, int32_t B, int32_t H, int32_t W, int32_t Hr,
+                      int32_t Wr, int32_t heads, int32_t dilation, float scale, int32_t dtype, void* stream);
 
 /* Fused residual + LayerScale + LayerNorm around the NAT layer's dense ops (SegNet/nat.py:140-153):
  *   a == NULL : y_out = LayerNorm(x)                                   (x_out ignored)

@@ -336,6 +336,34 @@ int ppn_na2d_bwd(const void* qkv, const float* rpb, const void* dout, void* dqkv
     return PPN_OK;
 }
 
+int64_t ppn_na2d_bwd_vpad_workspace(int32_t B, int32_t H, int32_t W, int32_t Hr, int32_t Wr, int32_t heads, int32_t dilation) {
+    if (B <= 0 || Hr <= 0 || Wr <= 0 || heads <= 0 || heads > 65535 || dilation < 1) return -1;
+    if (Hr > H || Wr > W || H < 7 * (long long)dilation || W < 7 * (long long)dilation) return -1;
+    if ((long long)B * heads * Hr * Wr >= (1LL << 40)) return -1;
+    // one workgroup per 8 x 8 region of the largest dilation group's padded sub-image, image and group: the grid's x extent
+    const long long hs = (H + (long long)dilation - 1) / dilation, ws = (W + (long long)dilation - 1) / dilation;
+    if (((hs + 7) / 8) * ((ws + 7) / 8) * B * dilation * dilation >= (1LL << 31)) return -1;
+    return ppn::na2d_bwd_vpad_workspace_floats(B, H, W, Hr, Wr, heads, dilation);
+}
+
+int ppn_na2d_bwd_vpad(const void* qkv, const void* pad_kv, const float* rpb, const void* dout, void* dqkv, float* dpad_kv, float* drpb,
+                      float* workspace, int64_t workspace_floats, int32_t B, int32_t H, int32_t W, int32_t Hr, int32_t Wr, int32_t heads,
+                      int32_t dilation, float scale, int32_t dtype, void* stream) {
+    if (!qkv || !pad_kv || !rpb || !dout || !dqkv || !dpad_kv || !drpb || !workspace) return PPN_E_INVALID;
+    if (dtype != 0 && dtype != 1) return PPN_E_INVALID;
+    if (!(scale > 0.0f) || scale > 3.0e38f) return PPN_E_INVALID;                        // NaN, inf, zero, negative
+    if ((((uintptr_t)qkv | (uintptr_t)pad_kv | (uintptr_t)rpb | (uintptr_t)dout | (uintptr_t)dqkv | (uintptr_t)dpad_kv | (uintptr_t)drpb |
+          (uintptr_t)workspace) & 15) != 0)
+        return PPN_E_INVALID;
+    const int64_t need = ppn_na2d_bwd_vpad_workspace(B, H, W, Hr, Wr, heads, dilation);  // every shape check lives there
+    if (need < 0 || workspace_floats < need) return PPN_E_INVALID;
+    const int e = ppn::na2d_bwd_vpad_launch(qkv, pad_kv, rpb, dout, dqkv, dpad_kv, drpb, workspace, B, H, W, Hr, Wr, heads, dilation, scale, dtype,
+                                            (hipStream_t)stream);
+    if (e == -1) return PPN_E_INVALID;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 static int na2d_checked(const void* qkv, const void* pad_kv, const float* rpb, void* out, int32_t B, int32_t H, int32_t W, int32_t Hr,
                         int32_t Wr, int32_t heads, int32_t dilation, float scale, int32_t dtype, void* stream) {
     if (!qkv || !rpb || !out || B <= 0 || heads <= 0 || dilation < 1 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;

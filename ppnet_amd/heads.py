@@ -13,13 +13,26 @@ from . import fused
 from .dense import mfma_weights, use_mfma_conv
 
 
+class _BatchNorm2d(nn.BatchNorm2d):
+    """nn.BatchNorm2d that takes its input in the dtype of its own parameters.  Under autocast the convolution in front hands it
+    bfloat16 activations while weight and running statistics stay float32; the statistics are float32 either way, and the cast
+    keeps the layer on the float32 channels_last path that float32 training takes (the mixed bfloat16 / float32 channels_last
+    form had never been run in this project: SETR-UP's training step under bfloat16 autocast ended in a segmentation fault inside
+    torch.batch_norm).  Same parameters, buffers and state-dict keys."""
+
+    def forward(self, x):
+        if self.weight is not None and x.dtype != self.weight.dtype:
+            x = x.to(self.weight.dtype)
+        return super().forward(x)
+
+
 class _ConvModule(nn.Sequential):
     """mmcv ConvModule(conv -> bn -> ReLU) with its parameter names `conv.*`, `bn.*` (conv has no bias under a norm)."""
 
     def __init__(self, cin, cout, k, dilation=1):
         super().__init__()
         self.add_module("conv", nn.Conv2d(cin, cout, k, 1, ((k - 1) // 2) * dilation, dilation, bias=False))
-        self.add_module("bn", nn.BatchNorm2d(cout))          # SyncBN reverts to BN outside distributed runs (SegNet/train.py:179-185)
+        self.add_module("bn", _BatchNorm2d(cout))            # SyncBN reverts to BN outside distributed runs (SegNet/train.py:179-185)
         self.add_module("activate", nn.ReLU(inplace=True))
 
 

@@ -1,17 +1,20 @@
 """Neighbourhood attention on MI355X: `NeighborhoodAttention2D` with the constructor, forward signature and
 state-dict keys (`qkv.*`, `rpb`, `proj.*`) of natten.NeighborhoodAttention2D as the reference uses it
-(SegNet/nat.py:111-120,144), backed by the fused HIP kernel (ppn_na2d_fwd). Forward only; no CPU fallback."""
+(SegNet/nat.py:111-120,144), backed by the fused HIP kernels (ppn_na2d_fwd*, ppn_na2d_bwd*); no CPU fallback."""
 import ctypes
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import _lib as L
 
 # Measurement hook (bench.py): a list here makes every kernel launch record (start event, end event, real tokens, channels)
 # on its stream, so the kernel's own duration — and with 8*C bytes per token its HBM fraction — can be read live.
 TIMING = None
+
+# The training path's launches on padded layers (na2d_autograd with pad_kv): forwards on ppn_na2d_fwd_vpad, backwards on
+# ppn_na2d_bwd_vpad.  Layers that need no padding are not counted.
+TRAIN_CALLS = {"fwd_vpad_kernel": 0, "bwd_vpad_kernel": 0}
 
 
 def na2d_forward(qkv, rpb, heads, dilation, scale, real_hw=None, pad_kv=None, padded_hw=None):
@@ -100,9 +103,50 @@ class _NA2DFunction(torch.autograd.Function):
         return dqkv, drpb.to(rpb_dtype), None, None, None
 
 
-def na2d_autograd(qkv, rpb, heads, dilation, scale):
-    """Differentiable neighbourhood attention on qkv [B,H,W,3C] (the caller pads to 7 * dilation first, as NATTEN's module does)."""
-    return _NA2DFunction.apply(qkv, rpb, heads, dilation, scale)
+class _NA2DVpadFunction(torch.autograd.Function):
+    """qkv [B,Hr,Wr,3C] (real tokens), pad_kv [3C] (the k / v of every padded position of the H x W grid), rpb [heads,13,13]
+    -> [B,Hr,Wr,C] on ppn_na2d_fwd_vpad; backward on ppn_na2d_bwd_vpad."""
+
+    @staticmethod
+    def forward(ctx, qkv, pad_kv, rpb, heads, dilation, scale, padded_hw):
+        qkv = qkv.contiguous()
+        pad = pad_kv.detach().to(qkv.dtype).contiguous()
+        rpb32 = rpb.detach().to(torch.float32).contiguous()
+        ctx.save_for_backward(qkv, pad, rpb32)
+        ctx.meta = (heads, dilation, scale, tuple(padded_hw), rpb.dtype, pad_kv.dtype)
+        TRAIN_CALLS["fwd_vpad_kernel"] += 1
+        return na2d_forward(qkv.detach(), rpb32, heads, dilation, scale, pad_kv=pad, padded_hw=padded_hw)
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, pad, rpb32 = ctx.saved_tensors
+        heads, dilation, scale, (H, W), rpb_dtype, pad_dtype = ctx.meta
+        B, Hr, Wr, C3 = qkv.shape
+        dout = dout.to(qkv.dtype).contiguous()
+        dqkv = torch.empty_like(qkv)
+        dpad = torch.empty(C3, dtype=torch.float32, device=qkv.device)
+        drpb = torch.empty_like(rpb32)
+        need = L.lib.ppn_na2d_bwd_vpad_workspace(B, H, W, Hr, Wr, heads, dilation)   # statistics of the real queries + partial sums
+        if need < 0:
+            raise ValueError(f"ppn_na2d_bwd_vpad: shape {(B, H, W, Hr, Wr, heads, dilation)} is outside the kernel")
+        ws = torch.empty(need, dtype=torch.float32, device=qkv.device)
+        dtype = {torch.float32: 0, torch.bfloat16: 1}[qkv.dtype]
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        with torch.cuda.device(qkv.device):
+            rc = L.lib.ppn_na2d_bwd_vpad(p(qkv), p(pad), p(rpb32), p(dout), p(dqkv), p(dpad), p(drpb), p(ws), need, B, H, W, Hr, Wr, heads,
+                                         dilation, float(scale), dtype, ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream))
+        L.check(rc, "ppn_na2d_bwd_vpad")
+        TRAIN_CALLS["bwd_vpad_kernel"] += 1
+        return dqkv, dpad.to(pad_dtype), drpb.to(rpb_dtype), None, None, None, None
+
+
+def na2d_autograd(qkv, rpb, heads, dilation, scale, pad_kv=None, padded_hw=None):
+    """Differentiable neighbourhood attention on qkv [B,H,W,3C] (the caller pads to 7 * dilation first, as NATTEN's module does).
+    With pad_kv [3C] and padded_hw=(H,W) the padding is virtual, as in na2d_forward: qkv holds the real tokens only, every other
+    position of the H x W grid has k / v = pad_kv, and pad_kv receives the padded positions' gradient (its q third: zeros)."""
+    if pad_kv is None:
+        return _NA2DFunction.apply(qkv, rpb, heads, dilation, scale)
+    return _NA2DVpadFunction.apply(qkv, pad_kv, rpb, heads, dilation, scale, padded_hw)
 
 
 class NeighborhoodAttention2D(nn.Module):
@@ -142,13 +186,18 @@ class NeighborhoodAttention2D(nn.Module):
             o = na2d_forward(self.qkv(x), self.rpb, self.num_heads, self.dilation, self.scale, real_hw)
             return self.proj_drop(self.proj(o))
         if torch.is_grad_enabled() and (x.requires_grad or self.rpb.requires_grad):
-            # training: NATTEN's module order — zero-pad bottom / right to kernel * dilation, qkv, NA over the padded grid
-            # (differentiable: ppn_na2d_bwd), crop, proj
+            # training: qkv, NA (differentiable: ppn_na2d_bwd), proj.  NATTEN's module zero-pads bottom / right to kernel * dilation
+            # before the projection; here the projection sees the real tokens only and the bias stands for every padded key / value
+            # in both directions (ppn_na2d_fwd_vpad / ppn_na2d_bwd_vpad): its share of the gradient reaches qkv.bias through the .to
             B, H, W, _ = x.shape
             pad = self.padded_hw(H, W)
-            xp = x if pad is None else F.pad(x, (0, 0, 0, pad[1] - W, 0, pad[0] - H))
-            o = na2d_autograd(self.qkv(xp), self.rpb, self.num_heads, self.dilation, self.scale)
-            return self.proj_drop(self.proj(o[:, :H, :W]))
+            qkv = self.qkv(x)
+            if pad is None:
+                o = na2d_autograd(qkv, self.rpb, self.num_heads, self.dilation, self.scale)
+            else:
+                bias = self.qkv.bias.to(qkv.dtype) if self.qkv.bias is not None else qkv.new_zeros(qkv.shape[-1])
+                o = na2d_autograd(qkv, self.rpb, self.num_heads, self.dilation, self.scale, pad_kv=bias, padded_hw=pad)
+            return self.proj_drop(self.proj(o))
         return self.proj_drop(self.proj(self.attend(x)))
 
     def _rpb_f32(self):

@@ -10,7 +10,8 @@ MMDistributedDataParallel = gradient all-reduce averaged over the ranks).
 
 What is native here: the training PAIRS come straight from the generator kernels on the device (stage A/B + ppn_label_masks:
 mask_space / mask_path / the rendered map — the reference re-reads them from image files, my_dataset.py:30-76), the
-neighbourhood attention's backward is the HIP kernel (ppn_na2d_bwd through na.na2d_autograd), so is the ViT backbone's global
+neighbourhood attention's backward is the HIP kernel (ppn_na2d_bwd through na.na2d_autograd; ppn_na2d_bwd_vpad on the layers
+NATTEN pads to 7 * dilation, which train on their real tokens), so is the ViT backbone's global
 attention's (ppn_mhsa_bwd through vit.mhsa_autograd: no N x N tensor saved, bitwise-reproducible gradients), and the gradient
 exchange is torch's DistributedDataParallel over RCCL with buckets sized for xGMI rings (few large all-reduces).  Every other op
 of the backward pass is a ROCm library call through autograd: the fused inference kernels are forward-only and step aside while
