@@ -313,10 +313,12 @@ int ppn_swin_wmsa_bwd(const void* qkv, const void* pad_kv, const float* rpb, con
  * VisionTransformer calls through mmcv's MultiheadAttention, SegNet/mmseg/backbones/vit.py:63-70,92-95):
  * out[b][n][h][:] = softmax_m(scale * q[b][n][h] . k[b][m][h]) . v[b][m][h], the sum over all N keys m of image b.
  * qkv [B][N][3][heads][head_dim] (each token row q | k | v: the order of in_proj_weight), out [B][N][heads][head_dim].
- * head_dim must be 64 (else PPN_E_UNSUPPORTED); any N >= 1.  NULL pointers, B / N / heads <= 0, a non-finite or non-positive
+ * head_dim must be 64 or 8 (else PPN_E_UNSUPPORTED); any N >= 1.  NULL pointers, B / N / heads <= 0, a non-finite or non-positive
  * scale, a dtype other than 0 / 1, buffers not 16-byte aligned and grids of 2^31 work-items or more return PPN_E_INVALID
- * before any HIP call.  dtype 0 = float32 (VALU), 1 = bfloat16 (flash-style on the matrix cores: float32 online softmax and
- * accumulation, the output rounded once). */
+ * before any HIP call.  head_dim 64 (mmseg's ViT): dtype 0 = float32 (VALU), 1 = bfloat16 (flash-style on the matrix cores:
+ * float32 online softmax and accumulation, the output rounded once).  head_dim 8 (GenNet's AE-ViT, csrc/mhsa_d8.hip): both data
+ * types on one flash-style VALU kernel, a query per lane with its 8 channels in registers, float32 online softmax and
+ * accumulation (bfloat16 converted on load, the output rounded once); nothing of size N x N reaches memory. */
 int ppn_mhsa_fwd(const void* qkv, void* out, int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, int32_t dtype,
                  void* stream);
 
@@ -326,11 +328,13 @@ int ppn_mhsa_fwd(const void* qkv, void* out, int32_t B, int32_t N, int32_t heads
  * Three passes (per-query softmax statistics and rowsum(dO o O) into the workspace; dK / dV per key block; dQ per query block):
  * P is recomputed, nothing of size N x N is stored, every output element has one writer and no atomics are used, so the
  * gradients are bitwise reproducible.  workspace: ppn_mhsa_bwd_workspace(B, N, heads) floats (2 * B * heads * N), 16-byte
- * aligned; workspace_floats is what the caller allocated and is checked.  head_dim must be 64 (else PPN_E_UNSUPPORTED); any
+ * aligned; workspace_floats is what the caller allocated and is checked.  head_dim must be 64 or 8 (else PPN_E_UNSUPPORTED); any
  * N >= 1.  NULL pointers, B / N / heads <= 0, a non-finite or non-positive scale, a dtype other than 0 / 1, buffers not 16-byte
  * aligned, a workspace that is too small and launches of 2^31 work-items or more return PPN_E_INVALID before any HIP call.
  * dtype 0 = float32 (VALU), 1 = bfloat16 (matrix cores: float32 softmax arithmetic and accumulation, P and dS rounded to
- * bfloat16 once each as operands, dqkv rounded once). */
+ * bfloat16 once each as operands, dqkv rounded once).  head_dim 8 (csrc/mhsa_d8.hip) runs the same three passes in the same
+ * workspace on VALU kernels for both data types: float32 arithmetic throughout (bfloat16 converted on load, P and dS never
+ * rounded, dqkv rounded once), the launch-size check against those kernels' own workgroup (256 rows, 128 work-items). */
 int64_t ppn_mhsa_bwd_workspace(int32_t B, int32_t N, int32_t heads);      /* floats; < 0: invalid shape */
 int ppn_mhsa_bwd(const void* qkv, const void* out, const void* dout, void* dqkv, float* workspace, int64_t workspace_floats,
                  int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, int32_t dtype, void* stream);

@@ -434,11 +434,14 @@ int ppn_mhsa_fwd(const void* qkv, void* out, int32_t B, int32_t N, int32_t heads
                  void* stream) {
     if (!qkv || !out || B <= 0 || N <= 0 || heads <= 0 || head_dim <= 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;
     if (!(scale > 0.0f) || scale > 3.0e38f) return PPN_E_INVALID;                        // NaN, inf, zero, negative
-    if (head_dim != 64) return PPN_E_UNSUPPORTED;
+    if (head_dim != 64 && head_dim != 8) return PPN_E_UNSUPPORTED;
     if ((((uintptr_t)qkv | (uintptr_t)out) & 15) != 0) return PPN_E_INVALID;              // 16-byte loads / stores
-    const long long qblock = dtype == 0 ? 64 : 128, threads = dtype == 0 ? 64 : 256;       // queries / work-items per workgroup
+    const bool d8 = head_dim == 8;                                                         // mhsa_d8.hip: one block shape, both dtypes
+    const long long qblock = d8 ? ppn::mhsa_d8_block_rows() : dtype == 0 ? 64 : 128;       // queries / work-items per workgroup
+    const long long threads = d8 ? ppn::mhsa_d8_block_threads() : dtype == 0 ? 64 : 256;
     if ((long long)B * heads * ((N + qblock - 1) / qblock) * threads >= 0x7fffffffLL) return PPN_E_INVALID;
-    const int e = ppn::mhsa_launch(qkv, out, B, N, heads, scale, dtype, (hipStream_t)stream);
+    const int e = d8 ? ppn::mhsa_d8_launch(qkv, out, B, N, heads, scale, dtype, (hipStream_t)stream)
+                     : ppn::mhsa_launch(qkv, out, B, N, heads, scale, dtype, (hipStream_t)stream);
     if (e != 0) return hip_fail((hipError_t)e);
     return PPN_OK;
 }
@@ -454,13 +457,16 @@ int ppn_mhsa_bwd(const void* qkv, const void* out, const void* dout, void* dqkv,
     if (!qkv || !out || !dout || !dqkv || !workspace || B <= 0 || N <= 0 || heads <= 0 || head_dim <= 0 || (dtype != 0 && dtype != 1))
         return PPN_E_INVALID;
     if (!(scale > 0.0f) || scale > 3.0e38f) return PPN_E_INVALID;                        // NaN, inf, zero, negative
-    if (head_dim != 64) return PPN_E_UNSUPPORTED;
+    if (head_dim != 64 && head_dim != 8) return PPN_E_UNSUPPORTED;
     if ((((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv | (uintptr_t)workspace) & 15) != 0) return PPN_E_INVALID;
-    const long long block = dtype == 0 ? 64 : 128, threads = dtype == 0 ? 128 : 256;       // rows / work-items per workgroup, every pass
+    const bool d8 = head_dim == 8;                                                         // mhsa_d8.hip: one block shape, both dtypes
+    const long long block = d8 ? ppn::mhsa_d8_block_rows() : dtype == 0 ? 64 : 128;        // rows / work-items per workgroup, every pass
+    const long long threads = d8 ? ppn::mhsa_d8_block_threads() : dtype == 0 ? 128 : 256;
     if ((long long)B * heads * ((N + block - 1) / block) * threads >= 0x7fffffffLL) return PPN_E_INVALID;
     const int64_t need = ppn_mhsa_bwd_workspace(B, N, heads);
     if (need < 0 || workspace_floats < need) return PPN_E_INVALID;
-    const int e = ppn::mhsa_bwd_launch(qkv, out, dout, dqkv, workspace, B, N, heads, scale, dtype, (hipStream_t)stream);
+    const int e = d8 ? ppn::mhsa_d8_bwd_launch(qkv, out, dout, dqkv, workspace, B, N, heads, scale, dtype, (hipStream_t)stream)
+                     : ppn::mhsa_bwd_launch(qkv, out, dout, dqkv, workspace, B, N, heads, scale, dtype, (hipStream_t)stream);
     if (e != 0) return hip_fail((hipError_t)e);
     return PPN_OK;
 }

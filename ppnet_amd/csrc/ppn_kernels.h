@@ -147,6 +147,12 @@ int mhsa_launch(const void* qkv, void* out, int B, int N, int heads, float scale
 long long mhsa_bwd_workspace_floats(int B, int N, int heads);
 int mhsa_bwd_launch(const void* qkv, const void* out, const void* dout, void* dqkv, float* workspace, int B, int N, int heads, float scale, int dtype,
                     hipStream_t stream);
+// head dim 8 (mhsa_d8.hip): the same layouts and workspace; rows and work-items per workgroup of every one of its kernels
+int mhsa_d8_block_rows();
+int mhsa_d8_block_threads();
+int mhsa_d8_launch(const void* qkv, void* out, int B, int N, int heads, float scale, int dtype, hipStream_t stream);
+int mhsa_d8_bwd_launch(const void* qkv, const void* out, const void* dout, void* dqkv, float* workspace, int B, int N, int heads, float scale,
+                       int dtype, hipStream_t stream);
 int swin_wmsa_launch(const void* qkv, const void* pad_kv, const float* rpb, void* out, int B, int H, int W, int heads, int shift, float scale,
                      int dtype, hipStream_t stream);
 long long swin_wmsa_bwd_workspace_floats(int heads);

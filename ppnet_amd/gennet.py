@@ -19,6 +19,7 @@ import torch.nn.functional as F
 
 from . import fused
 from .dense import drop_path
+from .vit import mhsa_autograd
 
 
 class _Attention(nn.Module):
@@ -31,6 +32,15 @@ class _Attention(nn.Module):
 
     def forward(self, x):
         B, N, C = x.shape
+        # GPU training (autograd recording, float32 / bfloat16 tokens, head dim 8): ppn_mhsa_fwd forward, ppn_mhsa_bwd backward
+        # (csrc/mhsa_d8.hip) - nothing of size N x N is saved, the gradients are bitwise reproducible.  PPNET_LIBRARY_ATTENTION
+        # (read here, at call time) keeps the library's attention below.
+        # The kernel sees the projection's output: under autocast that has the autocast dtype, not x's.
+        qkv_dtype = torch.get_autocast_dtype("cuda") if x.is_cuda and torch.is_autocast_enabled("cuda") else x.dtype
+        if (x.is_cuda and qkv_dtype in (torch.float32, torch.bfloat16) and C == 8 * self.num_heads
+                and fused.recording(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias)
+                and not os.environ.get("PPNET_LIBRARY_ATTENTION")):
+            return self.proj(mhsa_autograd(self.qkv(x), self.num_heads, self.scale))
         q, k, v = self.qkv(x).view(B, N, 3, self.num_heads, C // self.num_heads).permute(2, 0, 3, 1, 4)
         o = F.scaled_dot_product_attention(q, k, v, scale=self.scale)        # softmax(q k^T * scale) v, vit.py:103-109
         return self.proj(o.transpose(1, 2).reshape(B, N, C))

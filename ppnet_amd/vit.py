@@ -28,6 +28,8 @@ from .dense import drop_path, gpu_inference, linear
 from .swin import FFN, PatchEmbed
 
 HEAD_DIM = 64
+# head dims ppn_mhsa_fwd / ppn_mhsa_bwd take: 64 (mmseg's ViT: matrix cores) and 8 (GenNet's AE-ViT: csrc/mhsa_d8.hip)
+KERNEL_HEAD_DIMS = (8, 64)
 
 # Launch counters (tests / tools): how many attentions ran on the HIP forward kernel, how many backwards on ppn_mhsa_bwd.
 CALLS = {"kernel": 0, "bwd_kernel": 0}
@@ -36,13 +38,15 @@ TIMING = None
 
 
 def mhsa_forward(qkv, heads, scale):
-    """ppn_mhsa_fwd: qkv [B,N,3*heads*64] CUDA (float32 / bfloat16; each row q | k | v, each [heads][64]) -> [B,N,heads*64]."""
+    """ppn_mhsa_fwd: qkv [B,N,3*heads*D] CUDA (float32 / bfloat16; each row q | k | v, each [heads][D]) -> [B,N,heads*D]; the head
+    dim D = C // heads is read off the shape and must be 8 or 64."""
     if not qkv.is_cuda:
         raise RuntimeError("ppnet_amd.vit: the attention kernel runs on the GPU only (no CPU fallback)")
     B, N, C3 = qkv.shape
     C = C3 // 3
-    if C3 != 3 * C or C != heads * HEAD_DIM:
-        raise NotImplementedError(f"head dim {C // max(heads, 1)}: the kernel takes head dim {HEAD_DIM}")
+    hd = C // max(heads, 1)
+    if C3 != 3 * C or heads < 1 or C != heads * hd or hd not in KERNEL_HEAD_DIMS:
+        raise NotImplementedError(f"head dim {hd}: the kernel takes head dims {KERNEL_HEAD_DIMS}")
     dtype = {torch.float32: 0, torch.bfloat16: 1}.get(qkv.dtype)
     if dtype is None:
         raise NotImplementedError(f"dtype {qkv.dtype}")
@@ -54,7 +58,7 @@ def mhsa_forward(qkv, heads, scale):
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
     with torch.cuda.device(qkv.device):
-        rc = L.lib.ppn_mhsa_fwd(ctypes.c_void_p(qkv.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, N, heads, HEAD_DIM, float(scale), dtype,
+        rc = L.lib.ppn_mhsa_fwd(ctypes.c_void_p(qkv.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, N, heads, hd, float(scale), dtype,
                                 ctypes.c_void_p(stream.cuda_stream))
     L.check(rc, "ppn_mhsa_fwd")
     CALLS["kernel"] += 1
@@ -65,7 +69,7 @@ def mhsa_forward(qkv, heads, scale):
 
 
 class _MHSAFunction(torch.autograd.Function):
-    """qkv [B,N,3*heads*64] -> [B,N,heads*64] on ppn_mhsa_fwd; backward on ppn_mhsa_bwd.  Saves qkv and out, nothing else."""
+    """qkv [B,N,3*heads*D] -> [B,N,heads*D] (D = 8 or 64) on ppn_mhsa_fwd; backward on ppn_mhsa_bwd.  Saves qkv and out, nothing else."""
 
     @staticmethod
     def forward(ctx, qkv, heads, scale):
@@ -79,7 +83,7 @@ class _MHSAFunction(torch.autograd.Function):
     def backward(ctx, dout):
         qkv, out = ctx.saved_tensors
         heads, scale = ctx.meta
-        B, N, _ = qkv.shape
+        B, N, C3 = qkv.shape
         dout = dout.to(qkv.dtype).contiguous()
         dqkv = torch.empty_like(qkv)
         need = L.lib.ppn_mhsa_bwd_workspace(B, N, heads)                  # per-query softmax statistic and rowsum(dO o O); P is recomputed
@@ -89,7 +93,7 @@ class _MHSAFunction(torch.autograd.Function):
         dtype = {torch.float32: 0, torch.bfloat16: 1}[qkv.dtype]
         p = lambda t: ctypes.c_void_p(t.data_ptr())
         with torch.cuda.device(qkv.device):
-            rc = L.lib.ppn_mhsa_bwd(p(qkv), p(out), p(dout), p(dqkv), p(ws), need, B, N, heads, HEAD_DIM, float(scale), dtype,
+            rc = L.lib.ppn_mhsa_bwd(p(qkv), p(out), p(dout), p(dqkv), p(ws), need, B, N, heads, C3 // (3 * heads), float(scale), dtype,
                                     ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream))
         L.check(rc, "ppn_mhsa_bwd")
         CALLS["bwd_kernel"] += 1
@@ -97,7 +101,8 @@ class _MHSAFunction(torch.autograd.Function):
 
 
 def mhsa_autograd(qkv, heads, scale):
-    """Differentiable global attention on qkv [B,N,3*heads*64] CUDA (float32 / bfloat16): ppn_mhsa_fwd, and ppn_mhsa_bwd in backward."""
+    """Differentiable global attention on qkv [B,N,3*heads*D] CUDA (float32 / bfloat16; head dim D = 8 or 64, read off the shape):
+    ppn_mhsa_fwd, and ppn_mhsa_bwd in backward."""
     return _MHSAFunction.apply(qkv, heads, scale)
 
 
