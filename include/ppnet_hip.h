@@ -67,7 +67,8 @@ extern "C" {
  * Bumped whenever an entry point's argument list changes or an entry point is removed: 100 = rounds 1-3; 101 = round 4
  * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5; 106 = ppn_swin_wmsa_fwd; 107 = ppn_upsample2x_concat_nhwc;
  * 108 = ppn_mhsa_fwd; 109 = ppn_mhsa_bwd, ppn_mhsa_bwd_workspace; 110 = ppn_swin_wmsa_bwd, ppn_swin_wmsa_bwd_workspace;
- * 111 = ppn_na2d_bwd_vpad, ppn_na2d_bwd_vpad_workspace. */
+ * 111 = ppn_na2d_bwd_vpad, ppn_na2d_bwd_vpad_workspace.  ppn_resize_ce_workspace, ppn_resize_ce_fwd and ppn_resize_ce_bwd joined at
+ * 111 too: new symbols change no existing argument list and remove nothing, which is all the version guards against. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -338,6 +339,35 @@ int ppn_mhsa_fwd(const void* qkv, void* out, int32_t B, int32_t N, int32_t heads
 int64_t ppn_mhsa_bwd_workspace(int32_t B, int32_t N, int32_t heads);      /* floats; < 0: invalid shape */
 int ppn_mhsa_bwd(const void* qkv, const void* out, const void* dout, void* dqkv, float* workspace, int64_t workspace_floats,
                  int32_t B, int32_t N, int32_t heads, int32_t head_dim, float scale, int32_t dtype, void* stream);
+
+/* Training loss of a segmentation head without the resized logits: bilinear resize (torch's F.interpolate, align_corners=False,
+ * size given) of logit [B][C][h][w] (NCHW contiguous) to H x W, then cross-entropy against label [B][H][W] — what mmseg's
+ * BaseDecodeHead.losses composes from resize + CrossEntropyLoss + accuracy (decode_head.py:231-265).  Per full-resolution pixel:
+ * the C interpolated logits z_c, lse = log sum_c exp z_c (maximum subtracted), argmax (ties to the lowest class), loss lse - z_label.
+ * *loss = the sum over the valid pixels divided by ALL B H W pixels (an ignored pixel adds 0 and still counts in the divisor, as
+ * mmseg's mean does); *correct = the number of valid pixels whose argmax equals the label (an ignored pixel is never correct).
+ * A label equal to ignore_index OR outside [0, C) is ignored everywhere and never indexes memory — the one deliberate difference
+ * from the library, which raises a device-side assert on an out-of-range label.  lse [B][H][W] float32 is the only per-pixel
+ * state the backward needs; pass NULL when no backward is wanted and it is not written.  The sums have a fixed order (a tree per
+ * workgroup of 1024 pixels into the workspace, then one workgroup in double / int64) and no atomics: bitwise reproducible.
+ * workspace: ppn_resize_ce_workspace(B, H, W) floats = 2 * ceil(B * H * W / 1024) (a float32 loss sum and an int32 count per
+ * workgroup of 1024 pixels); workspace_floats is what the caller allocated and is checked.
+ * ppn_resize_ce_bwd: dlogit[b][c][y][x] = *grad_out / (B H W) * the sum over the valid pixels (Y, X) whose taps touch (y, x) of
+ * wy wx (exp(z_c(Y, X) - lse[Y][X]) - [label == c]), in gather form: one writer per element, dlogit (logit's layout and dtype) fully
+ * WRITTEN, fixed-order sums, no atomics.  logit, label and lse are what the forward read and wrote; grad_out is ONE float32 on the
+ * DEVICE (no host synchronisation).  Both calls use the same tap function, so they see the same z bit for bit.  float32 arithmetic
+ * for both logit dtypes (0 = float32, 1 = bfloat16: widened on load, dlogit rounded once); label_dtype 0 = uint8, 1 = int64.  Any
+ * C >= 1 and any sizes, up- or down-sampling.  NULL pointers (lse in the forward excepted), logit / dlogit / lse / workspace not
+ * 16-byte aligned, label / loss / correct / grad_out not naturally aligned, an extent <= 0, B C h w or B H W >= 2^31, a launch of
+ * 2^31 work-items or more, a dtype other than 0 / 1 and a workspace that is too small return PPN_E_INVALID before any HIP call. */
+int64_t ppn_resize_ce_workspace(int B, int H, int W);           /* floats; < 0 for invalid sizes */
+int ppn_resize_ce_fwd(const void* logit, const void* label, float* lse /* may be NULL: no backward wanted */,
+                      float* loss /* 1 */, int64_t* correct /* 1 */, float* workspace, int64_t workspace_floats,
+                      int B, int C, int h, int w, int H, int W, int ignore_index,
+                      int logit_dtype /* 0 f32, 1 bf16 */, int label_dtype /* 0 u8, 1 i64 */, void* stream);
+int ppn_resize_ce_bwd(const void* logit, const void* label, const float* lse, const float* grad_out /* device, 1 */,
+                      void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index,
+                      int logit_dtype, int label_dtype, void* stream);
 
 /* Backward of ppn_na2d_fwd (the gradient NATTEN's natten2dqkrpb / natten2dav backward kernels compute; first brick of the
  * training step, GenNet/train.py:93-147, SegNet/mmseg/apis/train.py:67-167).  qkv [B][H][W][3][heads][32] and rpb as in the

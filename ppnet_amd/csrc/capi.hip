@@ -471,6 +471,54 @@ int ppn_mhsa_bwd(const void* qkv, const void* out, const void* dout, void* dqkv,
     return PPN_OK;
 }
 
+int64_t ppn_resize_ce_workspace(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return -1;
+    if ((long long)H * W >= 0x80000000LL || (long long)B * ((long long)H * W) >= 0x80000000LL) return -1;      // pixel numbers are 32-bit
+    return ppn::resize_ce_workspace_floats(B, H, W);
+}
+
+// B C h w < 2^31, in steps that each stay within 64 bits
+static bool resize_ce_sizes_ok(int B, int C, int h, int w, int H, int W) {
+    if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return false;
+    const long long hw = (long long)h * w;
+    if (hw >= 0x80000000LL || (long long)C * hw >= 0x80000000LL || (long long)B * ((long long)C * hw) >= 0x80000000LL) return false;
+    return ppn_resize_ce_workspace(B, H, W) >= 0;
+}
+
+int ppn_resize_ce_fwd(const void* logit, const void* label, float* lse, float* loss, int64_t* correct, float* workspace, int64_t workspace_floats,
+                      int B, int C, int h, int w, int H, int W, int ignore_index, int logit_dtype, int label_dtype, void* stream) {
+    if (!logit || !label || !loss || !correct || !workspace) return PPN_E_INVALID;                    // lse may be NULL: no backward wanted
+    if ((logit_dtype != 0 && logit_dtype != 1) || (label_dtype != 0 && label_dtype != 1)) return PPN_E_INVALID;
+    if ((((uintptr_t)logit | (uintptr_t)lse | (uintptr_t)workspace) & 15) != 0) return PPN_E_INVALID;
+    if (((uintptr_t)loss & 3) != 0 || ((uintptr_t)correct & 7) != 0 || (label_dtype == 1 && ((uintptr_t)label & 7) != 0)) return PPN_E_INVALID;
+    if (!resize_ce_sizes_ok(B, C, h, w, H, W)) return PPN_E_INVALID;
+    // work-items of the forward launch: one per pixel in whole workgroups
+    const long long px = ppn::resize_ce_fwd_pixels(), groups = ((long long)B * H * W + px - 1) / px;
+    if (groups * ppn::resize_ce_threads() >= 0x7fffffffLL) return PPN_E_INVALID;
+    const int64_t need = ppn_resize_ce_workspace(B, H, W);
+    if (need < 0 || workspace_floats < need) return PPN_E_INVALID;
+    const int e = ppn::resize_ce_fwd_launch(logit, label, lse, loss, correct, workspace, B, C, h, w, H, W, ignore_index, logit_dtype, label_dtype,
+                                            (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_resize_ce_bwd(const void* logit, const void* label, const float* lse, const float* grad_out, void* dlogit, int B, int C, int h, int w,
+                      int H, int W, int ignore_index, int logit_dtype, int label_dtype, void* stream) {
+    if (!logit || !label || !lse || !grad_out || !dlogit) return PPN_E_INVALID;
+    if ((logit_dtype != 0 && logit_dtype != 1) || (label_dtype != 0 && label_dtype != 1)) return PPN_E_INVALID;
+    if ((((uintptr_t)logit | (uintptr_t)lse | (uintptr_t)dlogit) & 15) != 0) return PPN_E_INVALID;
+    if (((uintptr_t)grad_out & 3) != 0 || (label_dtype == 1 && ((uintptr_t)label & 7) != 0)) return PPN_E_INVALID;
+    if (!resize_ce_sizes_ok(B, C, h, w, H, W)) return PPN_E_INVALID;
+    // work-items of the backward launch: 1, 8 or 64 lanes per dlogit element in whole workgroups
+    const long long per = ppn::resize_ce_threads() / ppn::resize_ce_bwd_lanes(h, w, H, W);
+    if ((((long long)B * C * h * w + per - 1) / per) * ppn::resize_ce_threads() >= 0x7fffffffLL) return PPN_E_INVALID;
+    const int e = ppn::resize_ce_bwd_launch(logit, label, lse, grad_out, dlogit, B, C, h, w, H, W, ignore_index, logit_dtype, label_dtype,
+                                            (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_residual_layernorm(const void* x, const void* a, const void* gamma, const void* w, const void* b, void* x_out,
                            void* y_out, int64_t rows, int32_t C, float eps, int32_t dtype, void* stream) {
     return ppn_residual_layernorm_padded(x, a, gamma, w, b, x_out, y_out, rows, C, eps, dtype, 0, 0, 0, 0, stream);

@@ -158,6 +158,16 @@ int swin_wmsa_launch(const void* qkv, const void* pad_kv, const float* rpb, void
 long long swin_wmsa_bwd_workspace_floats(int heads);
 int swin_wmsa_bwd_launch(const void* qkv, const void* pad_kv, const float* rpb, const void* dout, void* dqkv, float* dpad_kv, float* drpb,
                          float* workspace, int B, int H, int W, int heads, int shift, float scale, int dtype, hipStream_t stream);
+// resize_ce.hip: bilinear resize + cross-entropy loss of a segmentation head, forward and backward; pixels per forward workgroup,
+// work-items per workgroup of every kernel, and the lanes that share one output of the backward (1 / 8 / 64 by the resize ratio)
+int resize_ce_fwd_pixels();
+int resize_ce_threads();
+int resize_ce_bwd_lanes(int h, int w, int H, int W);
+long long resize_ce_workspace_floats(int B, int H, int W);
+int resize_ce_fwd_launch(const void* logit, const void* label, float* lse, float* loss, int64_t* correct, float* workspace, int B, int C, int h,
+                         int w, int H, int W, int ignore_index, int logit_dtype, int label_dtype, hipStream_t stream);
+int resize_ce_bwd_launch(const void* logit, const void* label, const float* lse, const float* grad_out, void* dlogit, int B, int C, int h, int w,
+                         int H, int W, int ignore_index, int logit_dtype, int label_dtype, hipStream_t stream);
 int na2d_dense7_launch(const void* qkv, const void* pad_kv, const float* rpb, void* out, int B, int H, int W, int Hr, int Wr, int heads, int dil,
                        float scale, hipStream_t stream);
 int gennet_dec_final_launch(const void* x, const void* wt, const float* bias, float slope, const float* w1, float bias1, void* y, int B, int H, int W,

@@ -1,9 +1,10 @@
 """Host side of the fused residual / LayerScale / LayerNorm kernel (ppn_residual_layernorm). GPU only.
 
 Inference runs the HIP kernels below.  When autograd is recording (a training step, ppnet_amd/train.py) the same functions
-compose differentiable torch ops instead — the fused kernels are forward-only; the hand-written backwards are the two
+compose differentiable torch ops instead — the fused kernels are forward-only; the hand-written backwards are the
 attentions': neighbourhood (ppn_na2d_bwd, na.na2d_autograd), ViT's global one (ppn_mhsa_bwd, vit.mhsa_autograd) and Swin's window one
-(ppn_swin_wmsa_bwd, swin.wmsa_autograd)."""
+(ppn_swin_wmsa_bwd, swin.wmsa_autograd) — and the heads' loss: bilinear resize + cross-entropy (ppn_resize_ce_bwd,
+resize_cross_entropy below)."""
 import ctypes
 
 import torch
@@ -692,3 +693,100 @@ def gennet_trunk(x_nchw_cl, params32, n_blocks):
                                          ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
     L.check(rc, "ppn_gennet_trunk_bf16")
     return y.permute(0, 3, 1, 2)
+
+
+# ---------------------------------------------------------------- the heads' training loss: bilinear resize + cross-entropy
+LOSS_CALLS = {"fwd": 0, "bwd": 0}        # launches of ppn_resize_ce_fwd / ppn_resize_ce_bwd (like vit.CALLS)
+_LABEL_DT = {torch.uint8: 0, torch.int64: 1}
+_INT32_END = 1 << 31
+RESIZE_CE_THREADS = 256                  # work-items per workgroup of every kernel of csrc/resize_ce.hip
+RESIZE_CE_FWD_PIXELS = 1024              # pixels per workgroup of its forward (the unit of ppn_resize_ce_workspace)
+
+
+def resize_ce_bwd_lanes(h, w, H, W):
+    """Lanes that share one dlogit element in ppn_resize_ce_bwd (csrc/resize_ce.hip: resize_ce_bwd_lanes, the same rule): by the
+    pixels whose taps touch a low-resolution element, about (2 H/h)(2 W/w).  A workgroup writes RESIZE_CE_THREADS / lanes elements."""
+    f = 2.0 * max(H / h, 1.0) * 2.0 * max(W / w, 1.0)
+    return 1 if f <= 16.0 else (8 if f <= 128.0 else 64)
+
+
+def resize_ce_ok(logit, labels):
+    """Whether ppn_resize_ce_fwd / _bwd take these tensors: CUDA float32 / bfloat16 logits [B,C,h,w], CUDA uint8 / int64 labels
+    [B,H,W] of the same batch on the same device, sizes inside the entry points' limits (include/ppnet_hip.h)."""
+    if not (logit.is_cuda and labels.is_cuda and logit.device == labels.device and logit.dtype in _DT and labels.dtype in _LABEL_DT):
+        return False
+    if logit.dim() != 4 or labels.dim() != 3 or labels.shape[0] != logit.shape[0] or min(*logit.shape, *labels.shape) < 1:
+        return False
+    B, C, h, w = logit.shape
+    H, W = labels.shape[-2:]
+    per = RESIZE_CE_THREADS // resize_ce_bwd_lanes(h, w, H, W)              # the backward launch below 2^31 work-items
+    return labels.numel() < _INT32_END and logit.numel() < _INT32_END and -(-logit.numel() // per) * RESIZE_CE_THREADS < _INT32_END - 1
+
+
+def _resize_ce_fwd(logit, labels, ignore_index, want_lse):
+    """One ppn_resize_ce_fwd on contiguous tensors: (loss 0-d float32, correct 0-d int64, lse [B,H,W] float32 or None)."""
+    B, C, h, w = logit.shape
+    H, W = labels.shape[-2:]
+    dev = logit.device
+    need = L.lib.ppn_resize_ce_workspace(B, H, W)
+    if need < 0:
+        raise L.PpnError(f"ppn_resize_ce_workspace: invalid sizes B={B} H={H} W={W}", -1)
+    ws = torch.empty(need, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    correct = torch.empty((), dtype=torch.int64, device=dev)
+    lse = torch.empty(B, H, W, dtype=torch.float32, device=dev) if want_lse else None
+    with torch.cuda.device(dev):
+        rc = L.lib.ppn_resize_ce_fwd(_p(logit), _p(labels), _p(lse), _p(loss), _p(correct), _p(ws), need, B, C, h, w, H, W, ignore_index,
+                                     _DT[logit.dtype], _LABEL_DT[labels.dtype], ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    L.check(rc, "ppn_resize_ce_fwd")
+    LOSS_CALLS["fwd"] += 1
+    return loss, correct, lse
+
+
+def _resize_ce_bwd(logit, labels, lse, grad_out, ignore_index):
+    """One ppn_resize_ce_bwd: dlogit in logit's layout and dtype; grad_out a float32 scalar on the device."""
+    B, C, h, w = logit.shape
+    H, W = labels.shape[-2:]
+    dlogit = torch.empty_like(logit)
+    with torch.cuda.device(logit.device):
+        rc = L.lib.ppn_resize_ce_bwd(_p(logit), _p(labels), _p(lse), _p(grad_out), _p(dlogit), B, C, h, w, H, W, ignore_index, _DT[logit.dtype],
+                                     _LABEL_DT[labels.dtype], ctypes.c_void_p(torch.cuda.current_stream(logit.device).cuda_stream))
+    L.check(rc, "ppn_resize_ce_bwd")
+    LOSS_CALLS["bwd"] += 1
+    return dlogit
+
+
+class _ResizeCEFunction(torch.autograd.Function):
+    """Saves logit, labels and the per-pixel log-sum-exp, nothing else."""
+
+    @staticmethod
+    def forward(ctx, logit, labels, ignore_index):
+        loss, correct, lse = _resize_ce_fwd(logit, labels, ignore_index, True)
+        ctx.save_for_backward(logit, labels, lse)
+        ctx.ignore_index = ignore_index
+        ctx.mark_non_differentiable(correct)
+        return loss, correct
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_correct):
+        logit, labels, lse = ctx.saved_tensors
+        g = grad_loss.to(dtype=torch.float32, device=logit.device).contiguous()          # stays on the device: no synchronisation
+        return _resize_ce_bwd(logit, labels, lse, g, ctx.ignore_index), None, None
+
+
+def resize_cross_entropy(logit, labels, ignore_index=255):
+    """(loss, correct) of a head's low-resolution logits [B,C,h,w] (float32 / bfloat16) against labels [B,H,W] (uint8 / int64):
+    the mean over ALL B*H*W pixels of the cross-entropy of the logits resized bilinearly (align_corners=False) to H x W — ignored
+    pixels add 0 and count in the divisor — as a 0-d float32 tensor differentiable w.r.t. `logit`, and the number of pixels whose
+    argmax equals the label as a 0-d int64 tensor.  The resized logits are never built (ppn_resize_ce_fwd / ppn_resize_ce_bwd); a
+    label outside [0, C) counts as ignored.  Without autograd recording the per-pixel buffer and the backward are skipped."""
+    if not (logit.is_cuda and labels.is_cuda):
+        raise RuntimeError("ppnet_amd.fused: GPU tensors only (no CPU fallback)")
+    if not resize_ce_ok(logit, labels):
+        raise ValueError(f"resize_cross_entropy: logits {tuple(logit.shape)} {logit.dtype} / labels {tuple(labels.shape)} {labels.dtype} "
+                         "are outside ppn_resize_ce_fwd's types and limits")
+    logit, labels = logit.contiguous(), labels.contiguous()
+    if torch.is_grad_enabled() and logit.requires_grad:
+        return _ResizeCEFunction.apply(logit, labels, int(ignore_index))
+    loss, correct, _ = _resize_ce_fwd(logit.detach(), labels, int(ignore_index), False)
+    return loss, correct

@@ -431,3 +431,16 @@ def decode_losses(logit, gt, loss_weight=1.0, ignore_index=255):
     with torch.no_grad():
         acc = (logit.argmax(1) == gt).float().sum() * (100.0 / gt.numel())
     return loss, acc
+
+
+def resized_decode_losses(logit_lowres, gt, loss_weight=1.0, ignore_index=255, align_corners=False):
+    """decode_losses of a head's LOW-resolution logits [B,C,h,w] resized bilinearly to the labels' size [B,H,W]: the same
+    (loss_ce, acc_seg).  CUDA float32 / bfloat16 logits with CUDA uint8 / int64 labels, align_corners False and sizes inside
+    ppn_resize_ce_fwd's limits run on the fused kernel pair (fused.resize_cross_entropy: the resized logits are never built, the
+    gradient reaches the low-resolution logits directly); PPNET_LIBRARY_LOSS=1 (read at call time), CPU tensors and everything else
+    take the library composition, F.interpolate of the float32 logits followed by decode_losses on int64 labels."""
+    if not align_corners and not os.environ.get("PPNET_LIBRARY_LOSS") and fused.resize_ce_ok(logit_lowres, gt):
+        mean, correct = fused.resize_cross_entropy(logit_lowres, gt, ignore_index)
+        return loss_weight * mean, correct.float() * (100.0 / gt.numel())        # (a count below 2^24 is exact in float32)
+    logit = F.interpolate(logit_lowres.float(), gt.shape[-2:], mode="bilinear", align_corners=align_corners)
+    return decode_losses(logit, gt.long(), loss_weight, ignore_index)

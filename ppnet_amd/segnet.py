@@ -15,7 +15,7 @@ from .configs import (DINAT_BASE, NAT_BASE_UPER, NAT_BASE_UPERPUP, SWIN_BASE_SET
 from .dense import (IMG_MEAN, IMG_STD, LIBRARY_GEMM_BELOW_C, LIBRARY_GEMM_FROM_C, drop_path, normalize_images)  # noqa: F401
 from .dense import accumulate as _accumulate, bias32 as _bias32, library_width as _library_width, linear as _linear  # noqa: F401
 from .dense import mfma_weights as _mfma_weights, own_gemm_ok as _own_gemm_ok, use_mfma_conv as _use_mfma_conv  # noqa: F401
-from .heads import FCNHead, SETRUPHead, UPerHead, UPerPUPHead, _ConvModule, _Upsample, decode_losses  # noqa: F401
+from .heads import FCNHead, SETRUPHead, UPerHead, UPerPUPHead, _ConvModule, _Upsample, decode_losses, resized_decode_losses  # noqa: F401
 from .na import NeighborhoodAttention2D  # noqa: F401
 from .nat import NAT, ConvDownsampler, ConvTokenizer, DiNAT, Mlp, NATBlock, NATLayer, _fold_doc  # noqa: F401
 from .swin import SwinTransformer
@@ -192,13 +192,15 @@ class SegNet(nn.Module):
         if self.prepared:
             raise RuntimeError("SegNet.prepare_inference() folded BatchNorm / LayerScale into the weights: build a fresh SegNet to train")
         feats = self.backbone(img)
-        gt = gt_semantic_seg.squeeze(1).long() if gt_semantic_seg.dim() == 4 else gt_semantic_seg.long()
+        gt = gt_semantic_seg.squeeze(1) if gt_semantic_seg.dim() == 4 else gt_semantic_seg
+        if gt.dtype != torch.uint8:                    # uint8 labels go to the loss kernel as they are
+            gt = gt.long()
         losses = {}
         heads = [("decode", self.decode_head, 1.0)] + [(f"aux_{i}" if isinstance(self.auxiliary_head, nn.ModuleList) else "aux", h, h.loss_weight)
                                                        for i, h in enumerate(self._aux_heads())]
         for name, head, w in heads:
-            logit = F.interpolate(head(feats).float(), gt.shape[-2:], mode="bilinear", align_corners=head.align_corners)
-            losses[f"{name}.loss_ce"], losses[f"{name}.acc_seg"] = decode_losses(logit, gt, w)
+            # the head's output in its own dtype: the resize and the loss are one kernel pair on the GPU (heads.resized_decode_losses)
+            losses[f"{name}.loss_ce"], losses[f"{name}.acc_seg"] = resized_decode_losses(head(feats), gt, w, align_corners=head.align_corners)
         return losses
 
 
