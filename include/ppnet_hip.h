@@ -68,7 +68,8 @@ extern "C" {
  * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5; 106 = ppn_swin_wmsa_fwd; 107 = ppn_upsample2x_concat_nhwc;
  * 108 = ppn_mhsa_fwd; 109 = ppn_mhsa_bwd, ppn_mhsa_bwd_workspace; 110 = ppn_swin_wmsa_bwd, ppn_swin_wmsa_bwd_workspace;
  * 111 = ppn_na2d_bwd_vpad, ppn_na2d_bwd_vpad_workspace.  ppn_resize_ce_workspace, ppn_resize_ce_fwd and ppn_resize_ce_bwd joined at
- * 111 too: new symbols change no existing argument list and remove nothing, which is all the version guards against. */
+ * 111 too, and so did ppn_seg_eval: new symbols change no existing argument list and remove nothing, which is all the version guards
+ * against. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -368,6 +369,29 @@ int ppn_resize_ce_fwd(const void* logit, const void* label, float* lse /* may be
 int ppn_resize_ce_bwd(const void* logit, const void* label, const float* lse, const float* grad_out /* device, 1 */,
                       void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index,
                       int logit_dtype, int label_dtype, void* stream);
+
+/* Evaluation of a segmentation head without the resized logits: the three per-class area histograms that mmseg's mIoU / mDice /
+ * mFscore are computed from (intersect_and_union, core/evaluation/metrics.py:26-86).  Per full-resolution pixel: the C logits of
+ * logit [B][C][h][w] (NCHW contiguous) interpolated bilinearly to H x W with ppn_resize_ce_fwd's own tap arithmetic (torch's float32
+ * align_corners=False rule, one shared inline function), and their argmax in ONE sweep over the channels with no exponentials (the
+ * argmax of the softmax is the argmax of the logits); ties go to the lowest class, so the prediction is bit for bit the argmax that
+ * ppn_resize_ce_fwd counts in *correct.  A NaN logit never wins (all NaN: class 0) — the one difference from torch.argmax, which
+ * treats NaN as the maximum.  areas [3][C] int64: areas[0][c] = valid pixels with pred == label == c (intersect), areas[1][c] =
+ * valid pixels with pred == c, areas[2][c] = valid pixels with label == c; union = areas[1] + areas[2] - areas[0].  A label equal
+ * to ignore_index OR outside [0, C) is ignored: it adds to none of the three and never indexes memory (mmseg masks by
+ * label != ignore_index only, so an out-of-range label that is not ignore_index would still count in ITS prediction histogram — the
+ * deliberate difference, ppn_resize_ce_fwd's rule).  pred [B][H][W] uint8, when not NULL, is WRITTEN for every pixel, ignored or
+ * not (any alignment; four pixels per store where the address allows).  areas is zeroed on the stream inside the call and needs no
+ * workspace; counts are integers (int32 per workgroup in LDS — wave ballots and popcounts per class for C <= 8, LDS integer atomics
+ * above —, then one 64-bit global atomic add per non-zero bin), so the result does not depend on the order: bitwise reproducible.
+ * float32 arithmetic for both logit dtypes (0 = float32, 1 = bfloat16: widened on load); label_dtype 0 = uint8, 1 = int64.  Any
+ * sizes, up- or down-sampling.  NULL logit / label / areas, logit not 16-byte aligned, areas not 8-byte aligned, label not naturally
+ * aligned, an extent <= 0, C > 256 (pred is uint8, the LDS histogram is fixed), B C h w or B H W >= 2^31, a launch of 2^31
+ * work-items or more and a dtype other than 0 / 1 return PPN_E_INVALID before any HIP call. */
+int ppn_seg_eval(const void* logit /* [B][C][h][w] f32 | bf16 */, const void* label /* [B][H][W] u8 | i64 */,
+                 uint8_t* pred /* [B][H][W], may be NULL */, int64_t* areas /* [3][C]: intersect | pred | label */,
+                 int B, int C, int h, int w, int H, int W, int ignore_index,
+                 int logit_dtype /* 0 f32, 1 bf16 */, int label_dtype /* 0 u8, 1 i64 */, void* stream);
 
 /* Backward of ppn_na2d_fwd (the gradient NATTEN's natten2dqkrpb / natten2dav backward kernels compute; first brick of the
  * training step, GenNet/train.py:93-147, SegNet/mmseg/apis/train.py:67-167).  qkv [B][H][W][3][heads][32] and rpb as in the

@@ -519,6 +519,21 @@ int ppn_resize_ce_bwd(const void* logit, const void* label, const float* lse, co
     return PPN_OK;
 }
 
+int ppn_seg_eval(const void* logit, const void* label, uint8_t* pred, int64_t* areas, int B, int C, int h, int w, int H, int W, int ignore_index,
+                 int logit_dtype, int label_dtype, void* stream) {
+    if (!logit || !label || !areas) return PPN_E_INVALID;                                             // pred may be NULL: histograms only
+    if ((logit_dtype != 0 && logit_dtype != 1) || (label_dtype != 0 && label_dtype != 1)) return PPN_E_INVALID;
+    if (((uintptr_t)logit & 15) != 0 || ((uintptr_t)areas & 7) != 0 || (label_dtype == 1 && ((uintptr_t)label & 7) != 0)) return PPN_E_INVALID;
+    if (!resize_ce_sizes_ok(B, C, h, w, H, W) || C > ppn::seg_eval_max_classes()) return PPN_E_INVALID;
+    // work-items of the launch: a workgroup per tile of pixels, at most seg_eval_max_groups of them
+    const long long px = ppn::seg_eval_pixels(), tiles = ((long long)B * H * W + px - 1) / px;
+    const long long groups = tiles < ppn::seg_eval_max_groups() ? tiles : ppn::seg_eval_max_groups();
+    if (tiles >= 0x7fffffffLL || groups * ppn::seg_eval_threads() >= 0x7fffffffLL) return PPN_E_INVALID;
+    const int e = ppn::seg_eval_launch(logit, label, pred, areas, B, C, h, w, H, W, ignore_index, logit_dtype, label_dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_residual_layernorm(const void* x, const void* a, const void* gamma, const void* w, const void* b, void* x_out,
                            void* y_out, int64_t rows, int32_t C, float eps, int32_t dtype, void* stream) {
     return ppn_residual_layernorm_padded(x, a, gamma, w, b, x_out, y_out, rows, C, eps, dtype, 0, 0, 0, 0, stream);

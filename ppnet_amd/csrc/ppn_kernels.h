@@ -168,6 +168,15 @@ int resize_ce_fwd_launch(const void* logit, const void* label, float* lse, float
                          int w, int H, int W, int ignore_index, int logit_dtype, int label_dtype, hipStream_t stream);
 int resize_ce_bwd_launch(const void* logit, const void* label, const float* lse, const float* grad_out, void* dlogit, int B, int C, int h, int w,
                          int H, int W, int ignore_index, int logit_dtype, int label_dtype, hipStream_t stream);
+// seg_eval.hip: bilinear resize + argmax + the three per-class area histograms of a segmentation evaluation; pixels per tile,
+// work-items per workgroup, the largest grid (a workgroup strides over the tiles) and the largest C (pred is uint8, the LDS
+// histogram is fixed)
+int seg_eval_pixels();
+int seg_eval_threads();
+int seg_eval_max_groups();
+int seg_eval_max_classes();
+int seg_eval_launch(const void* logit, const void* label, uint8_t* pred, int64_t* areas, int B, int C, int h, int w, int H, int W, int ignore_index,
+                    int logit_dtype, int label_dtype, hipStream_t stream);
 int na2d_dense7_launch(const void* qkv, const void* pad_kv, const float* rpb, void* out, int B, int H, int W, int Hr, int Wr, int heads, int dil,
                        float scale, hipStream_t stream);
 int gennet_dec_final_launch(const void* x, const void* wt, const float* bias, float slope, const float* w1, float bias1, void* y, int B, int H, int W,

@@ -7,7 +7,7 @@
 //   loss      = 1 / (B H W) sum_{valid (Y, X)} (lse - z_label)    an ignored pixel adds 0 and still counts in the divisor
 //   dlogit[b][c][y][x] = g / (B H W) sum_{valid (Y, X) whose taps touch (y, x)} wy wx (exp(z_c - lse) - [label == c])
 //
-// One inline function (bilinear_tap) gives the taps of a destination index to every kernel of the file — torch's float32 rule for
+// One inline function (bilinear_tap, resize_tap.h) gives the taps of a destination index to every kernel of the file — torch's float32 rule for
 // align_corners=False with the size given — so the forward and the backward see the same interpolated logit bit for bit (the build
 // has -ffp-contract=off: no kernel fuses the products differently).  All arithmetic is float32 — only the sums over many pixels (the
 // last stage of the loss, a dlogit element's footprint) are kept in double and rounded once; bfloat16 logits are widened on load
@@ -33,6 +33,7 @@
 #include <stdint.h>
 #include "ppn_device.h"
 #include "ppn_kernels.h"
+#include "resize_tap.h"
 
 namespace ppn {
 
@@ -41,46 +42,12 @@ constexpr int RCE_THREADS = 256;                       // work-items per workgro
 constexpr int RCE_FWD_PER_THREAD = 4;
 constexpr int RCE_FWD_PX = RCE_THREADS * RCE_FWD_PER_THREAD;   // pixels per forward workgroup
 
-struct Tap { int i0, i1; float l0, l1; };
-
-// torch's area_pixel_compute_source_index (align_corners=False, no scale factor given) in float32, and upsample_bilinear2d's taps
-__device__ __forceinline__ Tap bilinear_tap(int X, int n_in, int n_out) {
-    const float scale = (float)n_in / (float)n_out;
-    float src = scale * ((float)X + 0.5f) - 0.5f;
-    if (src < 0.f) src = 0.f;
-    Tap t;
-    t.i0 = min((int)src, n_in - 1);                    // (int)src <= n_in - 1 in exact arithmetic; the min keeps every index inside
-    t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
-    t.l1 = src - (float)t.i0;
-    t.l0 = 1.f - t.l1;
-    return t;
-}
-
-template <typename T>
-__device__ __forceinline__ float ldf(const T* p) {
-    if constexpr (sizeof(T) == 4) return *p;
-    else return __uint_as_float((uint32_t)(*reinterpret_cast<const uint16_t*>(p)) << 16);      // bfloat16: the upper half, exact
-}
+// Tap, bilinear_tap, ldf, interp and valid_label: resize_tap.h (shared with seg_eval.hip, whose argmax is this file's)
 
 template <typename T>
 __device__ __forceinline__ void stf(T* p, float v) {
     if constexpr (sizeof(T) == 4) *p = v;
     else *p = (__bf16)v;                                                                       // rounded to nearest even, once
-}
-
-// the one interpolated logit of the file: plane = logit[b][c], rows r0 / r1 = i0 * w / i1 * w of the Y tap
-template <typename T>
-__device__ __forceinline__ float interp(const T* plane, int r0, int r1, const Tap& ty, const Tap& tx) {
-    const float z00 = ldf(plane + r0 + tx.i0), z01 = ldf(plane + r0 + tx.i1);
-    const float z10 = ldf(plane + r1 + tx.i0), z11 = ldf(plane + r1 + tx.i1);
-    return ty.l0 * (tx.l0 * z00 + tx.l1 * z01) + ty.l1 * (tx.l0 * z10 + tx.l1 * z11);
-}
-
-// label of a pixel, or -1 when it is ignored (ignore_index, or outside [0, C))
-template <typename LT>
-__device__ __forceinline__ int valid_label(const LT* label, size_t p, int C, int ignore_index) {
-    const long long v = (long long)label[p];
-    return (v == (long long)ignore_index || v < 0 || v >= (long long)C) ? -1 : (int)v;
 }
 
 template <typename T, typename LT>

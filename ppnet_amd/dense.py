@@ -2,8 +2,9 @@
 kernels (ppn_gemm_bf16, ppn_conv3x3_mfma_bf16, through fused.py) or on the ROCm libraries through PyTorch, with the `PPNET_LIBRARY_*`
 A/B knobs (read at call time: tests and tools set them after import; PPNET_LIBRARY_ATTENTION likewise sends the training attention of
 GenNet's AE-ViT, gennet._Attention, to the library's scaled_dot_product_attention instead of ppn_mhsa_fwd / ppn_mhsa_bwd at head
-dim 8, and PPNET_LIBRARY_LOSS sends the heads' training loss, heads.resized_decode_losses, to F.interpolate + F.cross_entropy instead of
-ppn_resize_ce_fwd / ppn_resize_ce_bwd) — plus what every network file shares: stochastic depth, the "GPU inference" predicate, the image normalisation.  nat.py, swin.py, vit.py, heads.py and gennet.py import from here; none imports
+dim 8, PPNET_LIBRARY_LOSS sends the heads' training loss, heads.resized_decode_losses, to F.interpolate + F.cross_entropy instead of
+ppn_resize_ce_fwd / ppn_resize_ce_bwd, and PPNET_LIBRARY_EVAL sends the evaluation's area histograms, heads.resized_eval_areas, to
+F.interpolate + argmax + torch.bincount instead of ppn_seg_eval) — plus what every network file shares: stochastic depth, the "GPU inference" predicate, the image normalisation.  nat.py, swin.py, vit.py, heads.py and gennet.py import from here; none imports
 segnet.py, which re-exports these names under their earlier underscore spellings."""
 import os
 

@@ -790,3 +790,47 @@ def resize_cross_entropy(logit, labels, ignore_index=255):
         return _ResizeCEFunction.apply(logit, labels, int(ignore_index))
     loss, correct, _ = _resize_ce_fwd(logit.detach(), labels, int(ignore_index), False)
     return loss, correct
+
+
+# ---------------------------------------------------------------- the heads' evaluation: bilinear resize + argmax + area histograms
+EVAL_CALLS = {"fwd": 0}                  # launches of ppn_seg_eval (like LOSS_CALLS)
+SEG_EVAL_THREADS = 256                   # work-items per workgroup of csrc/seg_eval.hip
+SEG_EVAL_PIXELS = 1024                   # pixels per tile: four consecutive ones per work-item
+SEG_EVAL_MAX_GROUPS = 1024               # workgroups at most: beyond SEG_EVAL_MAX_GROUPS tiles a workgroup strides over several
+SEG_EVAL_BALLOT_CLASSES = 8              # C up to here counts with wave ballots; above, with LDS integer atomics
+SEG_EVAL_MAX_CLASSES = 256               # pred is uint8 and the LDS histogram is fixed
+
+
+def seg_eval_ok(logit, labels):
+    """Whether ppn_seg_eval takes these tensors: CUDA float32 / bfloat16 logits [B,C,h,w] with C <= 256, CUDA uint8 / int64 labels
+    [B,H,W] of the same batch on the same device, sizes inside the entry point's limits (include/ppnet_hip.h)."""
+    if not (logit.is_cuda and labels.is_cuda and logit.device == labels.device and logit.dtype in _DT and labels.dtype in _LABEL_DT):
+        return False
+    if logit.dim() != 4 or labels.dim() != 3 or labels.shape[0] != logit.shape[0] or min(*logit.shape, *labels.shape) < 1:
+        return False
+    return logit.shape[1] <= SEG_EVAL_MAX_CLASSES and labels.numel() < _INT32_END and logit.numel() < _INT32_END
+
+
+def seg_eval(logit, labels, ignore_index=255, want_pred=False):
+    """(areas, pred) of a head's low-resolution logits [B,C,h,w] (float32 / bfloat16) against labels [B,H,W] (uint8 / int64): areas
+    int64 [3,C] on the device — per class the valid pixels with pred == label (intersect), with pred == class, with label == class,
+    where pred is the argmax (ties to the lowest class, a NaN never wins) of the logits resized bilinearly (align_corners=False) to
+    H x W — and pred uint8 [B,H,W] (every pixel, ignored or not) or None.  The resized logits are never built (ppn_seg_eval); a label
+    equal to ignore_index or outside [0, C) is ignored.  Nothing is read back: no host synchronisation."""
+    if not (logit.is_cuda and labels.is_cuda):
+        raise RuntimeError("ppnet_amd.fused: GPU tensors only (no CPU fallback)")
+    if not seg_eval_ok(logit, labels):
+        raise ValueError(f"seg_eval: logits {tuple(logit.shape)} {logit.dtype} / labels {tuple(labels.shape)} {labels.dtype} "
+                         "are outside ppn_seg_eval's types and limits")
+    logit, labels = logit.detach().contiguous(), labels.contiguous()
+    B, C, h, w = logit.shape
+    H, W = labels.shape[-2:]
+    dev = logit.device
+    areas = torch.empty(3, C, dtype=torch.int64, device=dev)
+    pred = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if want_pred else None
+    with torch.cuda.device(dev):
+        rc = L.lib.ppn_seg_eval(_p(logit), _p(labels), _p(pred), _p(areas), B, C, h, w, H, W, int(ignore_index), _DT[logit.dtype],
+                                _LABEL_DT[labels.dtype], ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    L.check(rc, "ppn_seg_eval")
+    EVAL_CALLS["fwd"] += 1
+    return areas, pred

@@ -444,3 +444,29 @@ def resized_decode_losses(logit_lowres, gt, loss_weight=1.0, ignore_index=255, a
         return loss_weight * mean, correct.float() * (100.0 / gt.numel())        # (a count below 2^24 is exact in float32)
     logit = F.interpolate(logit_lowres.float(), gt.shape[-2:], mode="bilinear", align_corners=align_corners)
     return decode_losses(logit, gt.long(), loss_weight, ignore_index)
+
+
+def eval_areas(pred, gt, num_classes, ignore_index=255):
+    """The three area histograms of an evaluation, int64 [3, num_classes] (intersect | prediction | label; union = prediction + label -
+    intersect), from argmax labels `pred` and ground truth `gt` of one shape — mmseg's intersect_and_union (core/evaluation/
+    metrics.py:26-86) with exact integer counts (torch.bincount; the reference's histc works on floats).  A label equal to
+    ignore_index OR outside [0, num_classes) is ignored: it adds to none of the three.  mmseg masks by label != ignore_index only, so
+    an out-of-range label would still count in its prediction histogram — the deliberate difference, ppn_seg_eval's rule."""
+    pred, gt = pred.reshape(-1).long(), gt.reshape(-1).long()
+    valid = (gt != ignore_index) & (gt >= 0) & (gt < num_classes)
+    pred, gt = pred[valid], gt[valid]
+    return torch.stack([torch.bincount(pred[pred == gt], minlength=num_classes), torch.bincount(pred, minlength=num_classes),
+                        torch.bincount(gt, minlength=num_classes)])
+
+
+def resized_eval_areas(logit_lowres, gt, ignore_index=255, align_corners=False):
+    """eval_areas of a head's LOW-resolution logits [B,C,h,w] resized bilinearly to the labels' size [B,H,W] and their argmax: int64
+    [3,C].  CUDA float32 / bfloat16 logits with CUDA uint8 / int64 labels, align_corners False, C <= 256 and sizes inside
+    ppn_seg_eval's limits run on the fused kernel (fused.seg_eval: neither the resized logits nor the labels' masks are built);
+    PPNET_LIBRARY_EVAL=1 (read at call time), CPU tensors and everything else take the library composition, F.interpolate of the
+    float32 logits, argmax and three bincounts."""
+    if not align_corners and not os.environ.get("PPNET_LIBRARY_EVAL") and fused.seg_eval_ok(logit_lowres, gt):
+        return fused.seg_eval(logit_lowres, gt, ignore_index)[0]
+    with torch.no_grad():
+        logit = F.interpolate(logit_lowres.float(), gt.shape[-2:], mode="bilinear", align_corners=align_corners)
+        return eval_areas(logit.argmax(1), gt, logit.shape[1], ignore_index)

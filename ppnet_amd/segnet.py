@@ -16,6 +16,7 @@ from .dense import (IMG_MEAN, IMG_STD, LIBRARY_GEMM_BELOW_C, LIBRARY_GEMM_FROM_C
 from .dense import accumulate as _accumulate, bias32 as _bias32, library_width as _library_width, linear as _linear  # noqa: F401
 from .dense import mfma_weights as _mfma_weights, own_gemm_ok as _own_gemm_ok, use_mfma_conv as _use_mfma_conv  # noqa: F401
 from .heads import FCNHead, SETRUPHead, UPerHead, UPerPUPHead, _ConvModule, _Upsample, decode_losses, resized_decode_losses  # noqa: F401
+from .heads import eval_areas, resized_eval_areas
 from .na import NeighborhoodAttention2D  # noqa: F401
 from .nat import NAT, ConvDownsampler, ConvTokenizer, DiNAT, Mlp, NATBlock, NATLayer, _fold_doc  # noqa: F401
 from .swin import SwinTransformer
@@ -202,6 +203,22 @@ class SegNet(nn.Module):
             # the head's output in its own dtype: the resize and the loss are one kernel pair on the GPU (heads.resized_decode_losses)
             losses[f"{name}.loss_ce"], losses[f"{name}.acc_seg"] = resized_decode_losses(head(feats), gt, w, align_corners=head.align_corners)
         return losses
+
+    @torch.no_grad()
+    def eval_areas(self, img, gt_semantic_seg, ignore_index=255):
+        """The area histograms that mmseg's evaluation sums over a dataset (intersect_and_union of the whole-image prediction,
+        core/evaluation/metrics.py:26-86): int64 [3, C] on img's device — intersect | prediction | label per class, for
+        evaluate.total_area_to_metrics.  Labels as in forward_train ([B,1,H,W] or [B,H,W]; uint8 as they are).  With labels of the
+        input's size the head's output goes to heads.resized_eval_areas in its own resolution and dtype — one kernel on the GPU
+        (ppn_seg_eval: no [B,C,H,W] logits, no softmax, no int64 argmax, no masks); labels of another size get encode_decode's
+        resize to the input size, then the resize to the labels (encoder_decoder.py:247-252) and the library composition."""
+        gt = gt_semantic_seg.squeeze(1) if gt_semantic_seg.dim() == 4 else gt_semantic_seg
+        if gt.dtype != torch.uint8:
+            gt = gt.long()
+        if tuple(gt.shape[-2:]) == tuple(img.shape[-2:]):
+            return resized_eval_areas(self.decode_head(self.backbone(img)), gt, ignore_index, align_corners=self.align_corners)
+        logit = F.interpolate(self.encode_decode(img).float(), gt.shape[-2:], mode="bilinear", align_corners=self.align_corners)
+        return eval_areas(logit.argmax(1), gt, logit.shape[1], ignore_index)
 
 
 def randomize_neutral_parameters(model, seed=0, gamma=(0.05, 0.3)):

@@ -7,7 +7,7 @@ linear warm-up; the reference starts from an ImageNet checkpoint, dinat_base.py:
 no network here and no such checkpoint, so this is a FROM-SCRATCH run of a bounded number of minutes: what the figure says is "the
 training step trains", not what a converged SegNet reaches).  Every step draws a fresh batch from the generator kernels
 (ppnet_amd.train.generator_pairs: occupancy codes -> normalised image, labels = mask_space).  Evaluation on a held-out seed: mean IoU of
-the two classes (mmseg's mIoU), pixel accuracy, and the chain SegNet labels -> the build's TRAINED GenNet (ppnet_amd/weights) -> 8-bit
+the two classes and pixel accuracy (mmseg's mIoU / aAcc, ppnet_amd.train.evaluate_segnet), and the chain SegNet labels -> the build's TRAINED GenNet (ppnet_amd/weights) -> 8-bit
 heat map -> extract_path + collision check -> the OMPL harness's success / length criterion (process_map.py:452-506,
 updated_geometric_planner.py:260-277), beside the same chain fed with the label masks.  The 400 MB checkpoint is not kept.
 
@@ -37,26 +37,24 @@ def chain_eval(torch, mask_u8, pb, mb, placements, R, gen):
 
 
 def evaluate(torch, net, dev, R, gen, paths_n=16, placements=8, seed=987654321):
-    from ppnet_amd import edage, fused, train
+    from ppnet_amd import edage, evaluate as EV, fused, train
     from ppnet_amd.segnet import IMG_MEAN, IMG_STD
     pb = edage.generate_paths(paths_n, R, 50.0, 3.0, seed=seed, device=dev)
     mb = edage.generate_maps(pb, placements, 5.0, 20, seed=seed)
     grid, space, _ = train.generator_pairs(pb, mb, placements)
+    # mmseg's metrics from the area histograms of the build's evaluation (train.evaluate_segnet: one ppn_seg_eval per batch)
+    m = train.evaluate_segnet(net, grid, space, batch=16, metrics=("mIoU",))
+    iou = [float(v) if v == v else 0.0 for v in m["IoU"]]                 # a class with no pixel on either side: 0, as before
     net.eval()
     labels = []
-    with torch.no_grad():
+    with torch.no_grad():                                                 # the labels themselves feed the planner chain below
         for i in range(0, grid.shape[0], 16):
             img = fused.grid_to_image(grid[i:i + 16], IMG_MEAN, IMG_STD, torch.float32)
             labels.append(net.encode_decode(img).argmax(1).to(torch.uint8))
     lab = torch.cat(labels)
     net.train()
     gt = space.to(torch.uint8)
-    ious = []
-    for c in (0, 1):
-        inter = ((lab == c) & (gt == c)).sum().item()
-        union = ((lab == c) | (gt == c)).sum().item()
-        ious.append(inter / max(union, 1))
-    out = {"mIoU": sum(ious) / 2, "IoU_free_corridor": ious[1], "IoU_background": ious[0], "pixel_acc": float((lab == gt).float().mean()),
+    out = {"mIoU": EV.summarize(m)["mIoU"], "IoU_free_corridor": iou[1], "IoU_background": iou[0], "pixel_acc": float(m["aAcc"]),
            "corridor_fraction_gt": float((gt == 1).float().mean()), "corridor_fraction_pred": float((lab == 1).float().mean())}
     out["chain_segnet_labels"] = chain_eval(torch, lab, pb, mb, placements, R, gen)
     out["chain_label_masks"] = chain_eval(torch, gt, pb, mb, placements, R, gen)
