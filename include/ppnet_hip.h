@@ -68,8 +68,8 @@ extern "C" {
  * (ppn_conv3x3_relu_classify2_bf16 gained `partial`); 105 = round 5; 106 = ppn_swin_wmsa_fwd; 107 = ppn_upsample2x_concat_nhwc;
  * 108 = ppn_mhsa_fwd; 109 = ppn_mhsa_bwd, ppn_mhsa_bwd_workspace; 110 = ppn_swin_wmsa_bwd, ppn_swin_wmsa_bwd_workspace;
  * 111 = ppn_na2d_bwd_vpad, ppn_na2d_bwd_vpad_workspace.  ppn_resize_ce_workspace, ppn_resize_ce_fwd and ppn_resize_ce_bwd joined at
- * 111 too, and so did ppn_seg_eval: new symbols change no existing argument list and remove nothing, which is all the version guards
- * against. */
+ * 111 too, and so did ppn_seg_eval and ppn_augment_params / ppn_augment_codes / ppn_augment_rgb: new symbols change no existing
+ * argument list and remove nothing, which is all the version guards against. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -491,6 +491,56 @@ int ppn_adaptive_pools_nhwc(const void* x, void* const* y, const int32_t* scales
  * mean3 / std3 are HOST pointers to three floats; n_pixels a multiple of 8. */
 int ppn_grid_to_image(const uint8_t* grid, void* img, int64_t n_pixels, const float* mean3, const float* std3, int32_t dtype,
                       void* stream);
+/* SegNet's TRAINING input: the reference's train_pipeline (SegNet/configs/_base_/datasets/planning_seg.py:18-27) RandomFlip(0.5) ->
+ * PhotoMetricDistortion -> Normalize -> Pad(size, pad_val 0, seg_pad_val 255) on the device, image and labels together.
+ *
+ * Per-image parameters: params [B][PPN_AUG_PARAM_WORDS] 32-bit words = { flags (PPN_AUG_* bits), beta float32 (brightness),
+ * alpha float32 (contrast), alpha_s float32 (saturation), delta int32 (hue), 0, 0, 0 }; any caller may fill them, ppn_augment_params
+ * draws them.  The colour function on one BGR u8 pixel, in this order (mmseg/datasets/pipelines/transforms.py:835-940):
+ * brightness convert(x, 1, beta); contrast convert(x, alpha, 0) here unless PPN_AUG_CONTRAST_LAST; saturation BGR -> HSV,
+ * S = convert(S, alpha_s, 0), HSV -> BGR; hue BGR -> HSV, H = (H + delta) mod 180 (non-negative), HSV -> BGR (a second round trip, as
+ * in the reference); contrast when PPN_AUG_CONTRAST_LAST.  A step whose flag is off is skipped entirely.  convert(x, a, b) =
+ * float32(x) * a + b as two separately rounded float32 operations, clipped to [0, 255], truncated toward zero.  HSV is the documented
+ * OpenCV 8-bit form (H in [0, 180)) in exact integer arithmetic with round-half-up (DESIGN.md 18 states it; OpenCV's own roundings
+ * are NOT pinned against it).  Then channel c of RGB: (float32(v) - mean3[c]) / std3[c], IEEE float32 (ppn_grid_to_image's
+ * expression), rounded to bfloat16 for dtype 1.  With PPN_AUG_FLIP output column x shows source column W - 1 - x, image and label
+ * alike.  img_out [B][Ho][Wo][3] (NHWC) and label_out [B][Ho][Wo] are WRITTEN for every pixel: outside the H x W source the image is
+ * 0.0 and the label seg_pad_val (its low 8 bits).  Labels: label_in [B][H][W] u8 and label_out both given, or both NULL.
+ * mean3 / std3 are HOST pointers to three floats.  W % 8 == 0, Wo % 8 == 0, Ho >= H, Wo >= W.
+ *
+ * ppn_augment_params: one work-item per image; draws d0..d9 = Philox doubles (numpy recipe) of (seed, stream 5, instance
+ * first_instance + b), fixed slots: d0 < flip_ratio flip; d1 < 0.5 brightness on, beta = -brightness_delta + 2 brightness_delta d2;
+ * d3 < 0.5 contrast first (else PPN_AUG_CONTRAST_LAST); d4 < 0.5 contrast on, alpha = contrast_lo + (contrast_hi - contrast_lo) d5;
+ * d6 < 0.5 saturation on, alpha_s likewise from d7; d8 < 0.5 hue on, delta = -hue_delta + floor(2 hue_delta d9) (the upper bound is
+ * excluded, as numpy.random.randint does).  Double arithmetic, stored as float32 / int32.  The reference's defaults: 0.5, 32,
+ * 0.5, 1.5, 0.5, 1.5, 18.
+ * ppn_augment_codes: grid [B][H][W] u8 occupancy codes, rendered with ppn_grid_to_image's palette (free white, marker red, anything
+ * else black).  A distorted palette image still has three colours per image: each workgroup distorts the three colours once and a
+ * pixel costs selects only.  With flags 0 and Ho == H, Wo == W the image is bit for bit ppn_grid_to_image's.
+ * ppn_augment_rgb: rgb [B][H][W][3] u8, channel order RGB; the same colour function per pixel.
+ * NULL grid / rgb / params / img_out / mean3 / std3, one label pointer without the other, a size <= 0, W % 8 or Wo % 8 != 0, Ho < H,
+ * Wo < W, a dtype other than 0 / 1, grid / rgb / label_in / label_out not 8-byte aligned, img_out / params not 16-byte aligned,
+ * B Ho Wo 3 >= 2^31 or a launch of 2^31 work-items or more return PPN_E_INVALID before any HIP call; so do, for ppn_augment_params,
+ * NULL / misaligned params, B <= 0 and a setting outside flip_ratio in [0, 1], brightness_delta in [0, 255],
+ * 0 <= lo <= hi <= 255, hue_delta in [0, 180]. */
+#define PPN_AUG_FLIP            1u
+#define PPN_AUG_BRIGHTNESS      2u
+#define PPN_AUG_CONTRAST        4u
+#define PPN_AUG_CONTRAST_LAST   8u
+#define PPN_AUG_SATURATION     16u
+#define PPN_AUG_HUE            32u
+#define PPN_AUG_PARAM_WORDS     8
+int ppn_augment_params(uint64_t seed, uint64_t first_instance, int B, double flip_ratio, double brightness_delta, double contrast_lo,
+                       double contrast_hi, double saturation_lo, double saturation_hi, int hue_delta,
+                       uint32_t* params /* [B][8] */, void* stream);
+int ppn_augment_codes(const uint8_t* grid /* [B][H][W] */, const uint8_t* label_in /* [B][H][W], may be NULL */,
+                      const uint32_t* params /* [B][8] */, void* img_out /* [B][Ho][Wo][3] f32 | bf16 */,
+                      uint8_t* label_out /* [B][Ho][Wo], NULL with label_in */, int B, int H, int W, int Ho, int Wo,
+                      const float* mean3, const float* std3, int seg_pad_val, int dtype /* 0 f32, 1 bf16 */, void* stream);
+int ppn_augment_rgb(const uint8_t* rgb /* [B][H][W][3] */, const uint8_t* label_in /* [B][H][W], may be NULL */,
+                    const uint32_t* params /* [B][8] */, void* img_out /* [B][Ho][Wo][3] f32 | bf16 */,
+                    uint8_t* label_out /* [B][Ho][Wo], NULL with label_in */, int B, int H, int W, int Ho, int Wo,
+                    const float* mean3, const float* std3, int seg_pad_val, int dtype /* 0 f32, 1 bf16 */, void* stream);
 /* The segmentor's output tail for two classes (setr_up_head.py:78-80, encoder_decoder.py:76-79,242,257): logits [B][2][h][w]
  * (NCHW) -> bilinear x2 -> bilinear to [Ho][Wo] (both align_corners=False, each rounded to the logits' dtype as the
  * materialised tensors are) -> float32 softmax -> argmax, labels u8 [B][Ho][Wo] in {0,1}. */

@@ -56,7 +56,8 @@ EXPORTS = ("ppn_version", "ppn_error_string", "ppn_last_hip_error", "ppn_polyfit
            "ppn_extract_paths", "ppn_resize_bilinear_u8", "ppn_philox_doubles", "ppn_na2d_fwd", "ppn_na2d_fwd_padded", "ppn_na2d_fwd_vpad", "ppn_swin_wmsa_fwd", "ppn_swin_wmsa_bwd", "ppn_swin_wmsa_bwd_workspace", "ppn_mhsa_fwd", "ppn_mhsa_bwd", "ppn_mhsa_bwd_workspace", "ppn_na2d_bwd", "ppn_na2d_bwd_workspace", "ppn_na2d_bwd_vpad", "ppn_na2d_bwd_vpad_workspace", "ppn_residual_layernorm", "ppn_residual_layernorm_padded", "ppn_layernorm_offset", "ppn_upsample2x_nhwc", "ppn_resize_concat4_nhwc", "ppn_resize_concat_nhwc", "ppn_adaptive_pools_nhwc", "ppn_upsample2x_add_nhwc", "ppn_upsample2x_nhwc_bias", "ppn_upsample2x_concat_nhwc", "ppn_bias_act_nhwc", "ppn_seg_labels_2class", "ppn_grid_to_image", "ppn_conv3x3_c1_nhwc", "ppn_conv3x3_to1_nhwc",
            "ppn_conv3x3_mfma_bf16", "ppn_conv3x3_relu_classify2_bf16", "ppn_conv3x3_relu_classify2_slots", "ppn_gemm_bf16", "ppn_nat_gemm_bf16", "ppn_nat_gemm_partials", "ppn_row_stats_bf16", "ppn_nat_mlp_supported", "ppn_nat_mlp_pack_bf16", "ppn_nat_mlp_bf16", "ppn_gennet_conv_s2_bf16", "ppn_gennet_trunk_bf16",
            "ppn_assemble_paths", "ppn_plan_collision", "ppn_gennet_first_enc_bf16", "ppn_gennet_dec_final_bf16", "ppn_heatmap_u8", "ppn_tokenizer_conv1_codes_bf16", "ppn_tokenizer_codes_bf16", "ppn_nat128_ln_qkv_bf16", "ppn_nat128_ln_mlp_bf16", "ppn_nat128_ln_mlp_add_bf16", "ppn_nat128_proj_add_bf16",
-           "ppn_resize_ce_workspace", "ppn_resize_ce_fwd", "ppn_resize_ce_bwd", "ppn_seg_eval")
+           "ppn_resize_ce_workspace", "ppn_resize_ce_fwd", "ppn_resize_ce_bwd", "ppn_seg_eval",
+           "ppn_augment_params", "ppn_augment_codes", "ppn_augment_rgb")
 
 
 def _load():
@@ -164,6 +165,9 @@ def _load():
     lib.ppn_resize_ce_fwd.argtypes = [_p, _p, _p, _p, _p, _p, C.c_int64] + [C.c_int] * 9 + [_p]
     lib.ppn_resize_ce_bwd.argtypes = [_p, _p, _p, _p, _p] + [C.c_int] * 9 + [_p]
     lib.ppn_seg_eval.argtypes = [_p, _p, _p, _p] + [C.c_int] * 9 + [_p]
+    lib.ppn_augment_params.argtypes = [C.c_uint64, C.c_uint64, C.c_int] + [C.c_double] * 6 + [C.c_int, _p, _p]
+    lib.ppn_augment_codes.argtypes = [_p, _p, _p, _p, _p] + [C.c_int] * 5 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, _p]
+    lib.ppn_augment_rgb.argtypes = lib.ppn_augment_codes.argtypes
     lib.ppn_label_masks.argtypes = [C.POINTER(PathsStruct), C.POINTER(MapsStruct), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     _p, _p, _p]
     for name in EXPORTS:

@@ -643,6 +643,53 @@ int ppn_grid_to_image(const uint8_t* grid, void* img, int64_t n_pixels, const fl
     return PPN_OK;
 }
 
+// B H W, B Ho Wo and the image's B Ho Wo 3 elements below 2^31, in steps that each stay within 64 bits
+static bool augment_args_ok(const void* in, const uint8_t* label_in, const uint32_t* params, const void* img_out, const uint8_t* label_out, int B,
+                            int H, int W, int Ho, int Wo, const float* mean3, const float* std3, int dtype) {
+    if (!in || !params || !img_out || !mean3 || !std3) return false;
+    if ((label_in == nullptr) != (label_out == nullptr)) return false;                                // labels: both or neither
+    if (B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || (W % 8) != 0 || (Wo % 8) != 0 || Ho < H || Wo < W) return false;
+    if (dtype != 0 && dtype != 1) return false;
+    if ((((uintptr_t)in | (uintptr_t)label_in | (uintptr_t)label_out) & 7) != 0) return false;        // eight pixels per load / store
+    if ((((uintptr_t)img_out | (uintptr_t)params) & 15) != 0) return false;
+    const long long px = (long long)Ho * Wo;
+    if (px >= 0x80000000LL || (long long)B * px >= 0x80000000LL || 3 * ((long long)B * px) >= 0x80000000LL) return false;
+    // work-items of the launch: whole workgroups per image
+    const long long per = ppn::augment_pixels(), groups = (px + per - 1) / per;
+    return (long long)B * groups * ppn::augment_threads() < 0x7fffffffLL;
+}
+
+int ppn_augment_params(uint64_t seed, uint64_t first_instance, int B, double flip_ratio, double brightness_delta, double contrast_lo,
+                       double contrast_hi, double saturation_lo, double saturation_hi, int hue_delta, uint32_t* params, void* stream) {
+    if (!params || ((uintptr_t)params & 15) != 0 || B <= 0 || (long long)B * PPN_AUG_PARAM_WORDS >= 0x80000000LL) return PPN_E_INVALID;
+    if (!(flip_ratio >= 0.0 && flip_ratio <= 1.0) || !(brightness_delta >= 0.0 && brightness_delta <= 255.0)) return PPN_E_INVALID;
+    if (!(contrast_lo >= 0.0 && contrast_hi >= contrast_lo && contrast_hi <= 255.0)) return PPN_E_INVALID;
+    if (!(saturation_lo >= 0.0 && saturation_hi >= saturation_lo && saturation_hi <= 255.0)) return PPN_E_INVALID;
+    if (hue_delta < 0 || hue_delta > 180) return PPN_E_INVALID;
+    const int e = ppn::augment_params_launch(seed, first_instance, B, flip_ratio, brightness_delta, contrast_lo, contrast_hi, saturation_lo,
+                                             saturation_hi, hue_delta, params, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_augment_codes(const uint8_t* grid, const uint8_t* label_in, const uint32_t* params, void* img_out, uint8_t* label_out, int B, int H, int W,
+                      int Ho, int Wo, const float* mean3, const float* std3, int seg_pad_val, int dtype, void* stream) {
+    if (!augment_args_ok(grid, label_in, params, img_out, label_out, B, H, W, Ho, Wo, mean3, std3, dtype)) return PPN_E_INVALID;
+    const int e = ppn::augment_launch(0, grid, label_in, params, img_out, label_out, B, H, W, Ho, Wo, mean3, std3, seg_pad_val, dtype,
+                                      (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_augment_rgb(const uint8_t* rgb, const uint8_t* label_in, const uint32_t* params, void* img_out, uint8_t* label_out, int B, int H, int W,
+                    int Ho, int Wo, const float* mean3, const float* std3, int seg_pad_val, int dtype, void* stream) {
+    if (!augment_args_ok(rgb, label_in, params, img_out, label_out, B, H, W, Ho, Wo, mean3, std3, dtype)) return PPN_E_INVALID;
+    const int e = ppn::augment_launch(1, rgb, label_in, params, img_out, label_out, B, H, W, Ho, Wo, mean3, std3, seg_pad_val, dtype,
+                                      (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_seg_labels_2class(const void* logits, uint8_t* labels, int32_t B, int32_t h, int32_t w, int32_t Ho, int32_t Wo, int32_t dtype,
                           void* stream) {
     if (!logits || !labels || B <= 0 || h <= 0 || w <= 0 || Ho <= 0 || Wo <= 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;

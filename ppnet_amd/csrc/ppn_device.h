@@ -24,7 +24,7 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 
 // ------------------------------------------------------------------------------------ Philox
 // Salmon et al. SC'11, Random123 constants; counter = (block, inst_hi, inst_lo, stream).
-enum : uint32_t { STREAM_PATH = 1, STREAM_POCKET = 2, STREAM_PLACE = 3, STREAM_OBST = 4 };
+enum : uint32_t { STREAM_PATH = 1, STREAM_POCKET = 2, STREAM_PLACE = 3, STREAM_OBST = 4, STREAM_AUG = 5 };
 
 struct u32x4 { uint32_t x, y, z, w; };
 

@@ -177,6 +177,14 @@ int seg_eval_max_groups();
 int seg_eval_max_classes();
 int seg_eval_launch(const void* logit, const void* label, uint8_t* pred, int64_t* areas, int B, int C, int h, int w, int H, int W, int ignore_index,
                     int logit_dtype, int label_dtype, hipStream_t stream);
+// augment.hip: SegNet's training input (flip + photometric distortion + normalise + pad) from occupancy codes or u8 RGB images;
+// work-items per workgroup and output pixels per workgroup (a workgroup serves one image)
+int augment_threads();
+int augment_pixels();
+int augment_params_launch(uint64_t seed, uint64_t first_instance, int B, double flip_ratio, double brightness_delta, double contrast_lo,
+                          double contrast_hi, double saturation_lo, double saturation_hi, int hue_delta, uint32_t* params, hipStream_t stream);
+int augment_launch(int rgb, const uint8_t* in, const uint8_t* label_in, const uint32_t* params, void* img, uint8_t* label_out, int B, int H, int W,
+                   int Ho, int Wo, const float* mean, const float* stdv, int seg_pad_val, int dtype, hipStream_t stream);
 int na2d_dense7_launch(const void* qkv, const void* pad_kv, const float* rpb, void* out, int B, int H, int W, int Hr, int Wr, int heads, int dil,
                        float scale, hipStream_t stream);
 int gennet_dec_final_launch(const void* x, const void* wt, const float* bias, float slope, const float* w1, float bias1, void* y, int B, int H, int W,

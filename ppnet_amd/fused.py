@@ -334,6 +334,64 @@ def seg_labels_2class(logits_lo, out_hw):
     return labels
 
 
+AUG_FLIP, AUG_BRIGHTNESS, AUG_CONTRAST, AUG_CONTRAST_LAST, AUG_SATURATION, AUG_HUE = 1, 2, 4, 8, 16, 32   # include/ppnet_hip.h: PPN_AUG_*
+AUG_PARAM_WORDS = 8                      # flags, beta f32, alpha f32, alpha_s f32, delta i32, three reserved zeros
+
+
+def augment_params(seed, first_instance, B, device, flip_ratio=0.5, brightness_delta=32.0, contrast_range=(0.5, 1.5),
+                   saturation_range=(0.5, 1.5), hue_delta=18):
+    """int32 [B, 8] per-image parameters of augment_codes / augment_rgb, drawn on the device from Philox stream 5 with instance
+    first_instance + b (ppn_augment_params; the draw slots are in include/ppnet_hip.h).  The float32 words are held as their bits."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("ppnet_amd.fused: GPU tensors only (no CPU fallback)")
+    params = torch.empty(B, AUG_PARAM_WORDS, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        rc = L.lib.ppn_augment_params(int(seed) & (2 ** 64 - 1), int(first_instance) & (2 ** 64 - 1), B, flip_ratio, brightness_delta,
+                                      contrast_range[0], contrast_range[1], saturation_range[0], saturation_range[1], int(hue_delta),
+                                      _p(params), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    L.check(rc, "ppn_augment_params")
+    return params
+
+
+def _augment(entry, name, src, labels, params, mean, std, dtype, out_size, seg_pad_val):
+    if not src.is_cuda or not params.is_cuda or (labels is not None and not labels.is_cuda):
+        raise RuntimeError("ppnet_amd.fused: GPU tensors only (no CPU fallback)")
+    if src.dtype != torch.uint8 or (labels is not None and labels.dtype != torch.uint8) or params.dtype != torch.int32:
+        raise ValueError(f"{name}: uint8 input and labels, int32 parameters")
+    src, params = src.contiguous(), params.contiguous()
+    B, H, W = src.shape[:3]
+    Ho, Wo = (H, W) if out_size is None else out_size
+    if tuple(params.shape) != (B, AUG_PARAM_WORDS) or (labels is not None and tuple(labels.shape) != (B, H, W)):
+        raise ValueError(f"{name}: parameters {tuple(params.shape)} / labels {None if labels is None else tuple(labels.shape)} do not "
+                         f"belong to a batch of {B} images of {H} x {W}")
+    img = torch.empty(B, Ho, Wo, 3, dtype=dtype, device=src.device)
+    lab_in = labels.contiguous() if labels is not None else None
+    lab_out = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=src.device) if labels is not None else None
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    with torch.cuda.device(src.device):
+        rc = entry(_p(src), _p(lab_in), _p(params), _p(img), _p(lab_out), B, H, W, Ho, Wo, m3, s3, int(seg_pad_val), _DT[dtype],
+                   ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream))
+    L.check(rc, name)
+    return img.permute(0, 3, 1, 2), lab_out
+
+
+def augment_codes(grid_u8, labels, params, mean, std, dtype, out_size=None, seg_pad_val=255):
+    """SegNet's TRAINING input from stage B's u8 codes [B,H,W]: the reference's flip + photometric distortion + normalise + pad
+    with the per-image parameters `params` (augment_params), one kernel (ppn_augment_codes).  Returns (image: channels_last
+    [B,3,Ho,Wo] of `dtype`, labels u8 [B,Ho,Wo] flipped and padded with the image, or None when `labels` is None)."""
+    if grid_u8.dim() != 3:
+        raise ValueError(f"augment_codes: [B,H,W] codes, got {tuple(grid_u8.shape)}")
+    return _augment(L.lib.ppn_augment_codes, "ppn_augment_codes", grid_u8, labels, params, mean, std, dtype, out_size, seg_pad_val)
+
+
+def augment_rgb(rgb_u8, labels, params, mean, std, dtype, out_size=None, seg_pad_val=255):
+    """augment_codes for u8 RGB images [B,H,W,3] (ppn_augment_rgb): the same colour function on every pixel."""
+    if rgb_u8.dim() != 4 or rgb_u8.shape[-1] != 3:
+        raise ValueError(f"augment_rgb: [B,H,W,3] images, got {tuple(rgb_u8.shape)}")
+    return _augment(L.lib.ppn_augment_rgb, "ppn_augment_rgb", rgb_u8, labels, params, mean, std, dtype, out_size, seg_pad_val)
+
+
 def grid_to_image(grid_u8, mean, std, dtype):
     """Normalised SegNet input, channels_last [B,3,R,R] of `dtype`, from stage B's u8 codes [B,R,R] (ppn_grid_to_image)."""
     if not grid_u8.is_cuda:

@@ -151,14 +151,29 @@ def segnet_trainer(segnet, device=None, bucket_cap_mb=128, sync_bn=True):
     return data_parallel(_SegTrain(segnet), device, bucket_cap_mb)
 
 
-def segnet_train_step(trainer, optimizer, it, max_iters, grid_u8, mask_space, schedule=None):
+def segnet_train_step(trainer, optimizer, it, max_iters, grid_u8, mask_space, schedule=None, augment=None):
     """One iteration: the normalised image from the occupancy codes (ppn_grid_to_image, planning_seg.py:12-41), labels =
-    mask_space; lr by the warm-up poly schedule; SGD step.  Returns the loss (0-d tensor)."""
+    mask_space; lr by the warm-up poly schedule; SGD step.  Returns the loss (0-d tensor).
+
+    augment = an augment.SegAugment: the reference's train_pipeline (planning_seg.py:18-27: flip, photometric distortion, normalise,
+    pad) makes the image AND the labels of the step from the u8 codes [B,R,R] (or u8 RGB images [B,R,R,3]) in one kernel
+    (ppn_augment_codes / ppn_augment_rgb).  Image b of iteration `it` on rank r of w draws with the global index (it * w + r) * B + b,
+    so the same (seed, it) repeats its images and ranks draw different ones; labels padded with 255 are ignored by the loss."""
     from . import fused
     from .segnet import IMG_MEAN, IMG_STD
     trainer.train()
     dtype = next(trainer.parameters()).dtype
-    img = fused.grid_to_image(grid_u8, IMG_MEAN, IMG_STD, dtype) if grid_u8.dtype == torch.uint8 else grid_u8
+    if augment is not None:
+        import torch.distributed as dist
+        from . import augment as aug_mod
+        if grid_u8.dtype != torch.uint8:
+            raise ValueError("segnet_train_step: augment= takes u8 occupancy codes [B,R,R] or u8 RGB images [B,R,R,3]")
+        rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
+        B = grid_u8.shape[0]
+        params = aug_mod.draw_params(augment, (it * world + rank) * B, B, grid_u8.device)
+        img, mask_space = aug_mod.apply(augment, params, grid_u8, mask_space.to(torch.uint8), IMG_MEAN, IMG_STD, dtype)
+    else:
+        img = fused.grid_to_image(grid_u8, IMG_MEAN, IMG_STD, dtype) if grid_u8.dtype == torch.uint8 else grid_u8
     segnet_set_lr(optimizer, it, max_iters, **(schedule or {}))
     loss = trainer(img, mask_space)
     optimizer.zero_grad(set_to_none=True)

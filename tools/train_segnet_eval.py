@@ -72,8 +72,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=300)
     ap.add_argument("--eval-every", type=int, default=1000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--augment", action="store_true",
+                    help="train on the reference's train_pipeline (flip + photometric distortion, ppnet_amd.augment) instead of the bare palette image")
     args = ap.parse_args()
-    from ppnet_amd import edage, train
+    from ppnet_amd import augment, edage, train
     from ppnet_amd.gennet import AEViT, load_trained
     from ppnet_amd.segnet import SegNet
     dev = torch.device("cuda:0")
@@ -87,6 +89,7 @@ def main():
     gen.prepare_inference()
     gen.to(dev).to(torch.bfloat16)
     batch = args.batch_paths * args.batch_placements
+    aug = augment.SegAugment(seed=777) if args.augment else None
     lines = []
 
     def emit(rec):
@@ -99,7 +102,7 @@ def main():
                 f.write(__doc__.split("\n\n")[0] + "\n\n" + "\n".join(lines) + "\n")
 
     emit({"config": "DiNAT-B + SETR-UP from scratch, float32", "R": R, "batch": batch, "lr": args.lr, "warmup_iters": args.warmup,
-          "schedule_horizon": args.max_iters, "parameters": sum(p.numel() for p in net.parameters()), "minutes": args.minutes})
+          "schedule_horizon": args.max_iters, "augment": bool(args.augment), "parameters": sum(p.numel() for p in net.parameters()), "minutes": args.minutes})
     r0 = evaluate(torch, net, dev, R, gen)
     emit({"step": 0, **{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r0.items()}})
     t0 = time.time()
@@ -108,7 +111,7 @@ def main():
         pb = edage.generate_paths(args.batch_paths, R, 50.0, 3.0, seed=777, first_path_id=it * args.batch_paths, device=dev)
         mb = edage.generate_maps(pb, args.batch_placements, 5.0, 20, seed=777, first_map_id=it * batch)
         grid, space, _ = train.generator_pairs(pb, mb, args.batch_placements)
-        loss = train.segnet_train_step(trainer, opt, it, args.max_iters, grid, space, schedule=dict(warmup_iters=args.warmup))
+        loss = train.segnet_train_step(trainer, opt, it, args.max_iters, grid, space, schedule=dict(warmup_iters=args.warmup), augment=aug)
         it += 1
         if it % 50 == 0:
             loss_acc += float(loss); n_acc += 1
