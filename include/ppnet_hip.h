@@ -69,7 +69,8 @@ extern "C" {
  * 108 = ppn_mhsa_fwd; 109 = ppn_mhsa_bwd, ppn_mhsa_bwd_workspace; 110 = ppn_swin_wmsa_bwd, ppn_swin_wmsa_bwd_workspace;
  * 111 = ppn_na2d_bwd_vpad, ppn_na2d_bwd_vpad_workspace.  ppn_resize_ce_workspace, ppn_resize_ce_fwd and ppn_resize_ce_bwd joined at
  * 111 too, and so did ppn_seg_eval and ppn_augment_params / ppn_augment_codes / ppn_augment_rgb: new symbols change no existing
- * argument list and remove nothing, which is all the version guards against. */
+ * argument list and remove nothing, which is all the version guards against.  ppn_ohem_ce_workspace, ppn_ohem_ce_fwd and
+ * ppn_ohem_ce_bwd joined at 111 in the same way. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -392,6 +393,49 @@ int ppn_seg_eval(const void* logit /* [B][C][h][w] f32 | bf16 */, const void* la
                  uint8_t* pred /* [B][H][W], may be NULL */, int64_t* areas /* [3][C]: intersect | pred | label */,
                  int B, int C, int h, int w, int H, int W, int ignore_index,
                  int logit_dtype /* 0 f32, 1 bf16 */, int label_dtype /* 0 u8, 1 i64 */, void* stream);
+
+/* ppn_resize_ce_fwd / _bwd with mmseg's OHEMPixelSampler (core/seg/sampler/ohem_pixel_sampler.py:32-85) and CrossEntropyLoss's
+ * class_weight (losses/cross_entropy_loss.py:10-33): the same bilinear resize of logit [B][C][h][w] to H x W (the same tap
+ * arithmetic, so the same interpolated logits bit for bit), per valid pixel ce = lse - z_label and p = exp(z_label - lse), and a
+ * SELECTION of the hard pixels instead of the reference's softmax + gather + sort.  cw = class_weight [C] float32 on the device, or
+ * NULL = all ones.  With n_valid valid pixels and batch_kept = min_kept * B:
+ *   mode 1 (thresh given)  score = p;  t = max(ascending_sorted(p)[min(batch_kept, n_valid - 1)], thresh);  selected = p < t;
+ *                          n_valid == 0: t = thresh and nothing is selected
+ *   mode 2 (thresh None)   score = cw[label] ce;  t = the batch_kept-th largest score (the smallest when batch_kept >= n_valid);
+ *                          selected = score >= t: pixels that TIE with the cut are all kept — the reference keeps exactly batch_kept
+ *                          and leaves the choice among ties to an unstable sort, the one deliberate difference;  n_valid == 0: t = +inf
+ *   mode 0 (no sampler)    score = cw[label] ce;  t = -inf;  every valid pixel is selected (class weights only)
+ * *loss = 1 / (B H W) * the sum over the selected pixels of cw[label] ce — the mean over ALL pixels, as weight_reduce_loss with
+ * avg_factor None takes it.  counts [3] int64 = {correct (valid pixels whose argmax, ties to the lowest class, equals the label: not
+ * changed by the sampling), n_valid, n_kept (selected pixels)}.  *threshold = t, float32, computed and kept on the DEVICE: nothing is
+ * read back to the host.  mask [B][H][W] uint8, when not NULL, is WRITTEN for every pixel: 1 selected, 0 not.  lse and score
+ * [B][H][W] float32 are WRITTEN for every pixel and are what the backward reads; an ignored pixel (label == ignore_index or outside
+ * [0, C), which never indexes memory) has the score NaN — no comparison with it is true, so it is never selected, and the histograms
+ * skip it — a valid pixel's score that comes out NaN is stored as +inf, and -0 as +0.  The selection is a radix select of the k-th
+ * smallest score over a 32-bit key that orders as the floats do, in three digits of 11 | 11 | 10 bits: integer histograms in LDS (the
+ * bin of a wave's first live lane is added once per wave by a ballot, twice over, the lanes left one by one), one global integer
+ * atomic per non-zero bin and workgroup; the later passes read score only.  Every sum of floats has a fixed order (a tree per
+ * workgroup, then one workgroup in double / int64) and every atomic is an integer add: loss, threshold, mask and dlogit are bitwise
+ * reproducible.  workspace: ppn_ohem_ce_workspace(B, H, W) BYTES (the same for every valid size), 16-byte aligned, needs NO
+ * initialisation by the caller; workspace_bytes is what the caller allocated and is checked.
+ * ppn_ohem_ce_bwd: dlogit[b][c][y][x] = *grad_out / (B H W) * the sum over the SELECTED pixels (Y, X) whose taps touch (y, x) of
+ * wy wx cw[label] (exp(z_c - lse) - [label == c]), in ppn_resize_ce_bwd's gather form: one writer per element, dlogit fully WRITTEN,
+ * fixed-order sums, no atomics; `selected` is recomputed from score and *threshold (device), no weight tensor exists.  Same
+ * class_weight, mode and ignore_index as the forward.  float32 arithmetic for both logit dtypes (0 = float32, 1 = bfloat16: widened on
+ * load, dlogit rounded once); label_dtype 0 = uint8, 1 = int64.  NULL pointers (class_weight and mask excepted), logit / dlogit /
+ * lse / score / workspace not 16-byte aligned, the others not naturally aligned, an extent <= 0, B C h w or B H W >= 2^31, a launch
+ * of 2^31 work-items or more, a dtype other than 0 / 1, a mode other than 0 / 1 / 2, min_kept < 1 (modes 1, 2), thresh outside (0, 1]
+ * or NaN (mode 1) and a workspace that is too small return PPN_E_INVALID before any HIP call. */
+int64_t ppn_ohem_ce_workspace(int B, int H, int W);             /* bytes; < 0 for invalid sizes */
+int ppn_ohem_ce_fwd(const void* logit, const void* label, const float* class_weight /* [C] device, may be NULL */,
+                    float* lse /* [B][H][W] */, float* score /* [B][H][W] */, float* loss /* 1 */,
+                    int64_t* counts /* 3: correct, n_valid, n_kept */, float* threshold /* 1 */, uint8_t* mask /* [B][H][W], may be NULL */,
+                    void* workspace, int64_t workspace_bytes, int B, int C, int h, int w, int H, int W, int ignore_index,
+                    int mode /* 0 none, 1 thresh, 2 top-k */, float thresh, int min_kept,
+                    int logit_dtype /* 0 f32, 1 bf16 */, int label_dtype /* 0 u8, 1 i64 */, void* stream);
+int ppn_ohem_ce_bwd(const void* logit, const void* label, const float* class_weight, const float* lse, const float* score,
+                    const float* threshold /* device, 1 */, const float* grad_out /* device, 1 */, void* dlogit,
+                    int B, int C, int h, int w, int H, int W, int ignore_index, int mode, int logit_dtype, int label_dtype, void* stream);
 
 /* Backward of ppn_na2d_fwd (the gradient NATTEN's natten2dqkrpb / natten2dav backward kernels compute; first brick of the
  * training step, GenNet/train.py:93-147, SegNet/mmseg/apis/train.py:67-167).  qkv [B][H][W][3][heads][32] and rpb as in the

@@ -57,7 +57,8 @@ EXPORTS = ("ppn_version", "ppn_error_string", "ppn_last_hip_error", "ppn_polyfit
            "ppn_conv3x3_mfma_bf16", "ppn_conv3x3_relu_classify2_bf16", "ppn_conv3x3_relu_classify2_slots", "ppn_gemm_bf16", "ppn_nat_gemm_bf16", "ppn_nat_gemm_partials", "ppn_row_stats_bf16", "ppn_nat_mlp_supported", "ppn_nat_mlp_pack_bf16", "ppn_nat_mlp_bf16", "ppn_gennet_conv_s2_bf16", "ppn_gennet_trunk_bf16",
            "ppn_assemble_paths", "ppn_plan_collision", "ppn_gennet_first_enc_bf16", "ppn_gennet_dec_final_bf16", "ppn_heatmap_u8", "ppn_tokenizer_conv1_codes_bf16", "ppn_tokenizer_codes_bf16", "ppn_nat128_ln_qkv_bf16", "ppn_nat128_ln_mlp_bf16", "ppn_nat128_ln_mlp_add_bf16", "ppn_nat128_proj_add_bf16",
            "ppn_resize_ce_workspace", "ppn_resize_ce_fwd", "ppn_resize_ce_bwd", "ppn_seg_eval",
-           "ppn_augment_params", "ppn_augment_codes", "ppn_augment_rgb")
+           "ppn_augment_params", "ppn_augment_codes", "ppn_augment_rgb",
+           "ppn_ohem_ce_workspace", "ppn_ohem_ce_fwd", "ppn_ohem_ce_bwd")
 
 
 def _load():
@@ -165,6 +166,10 @@ def _load():
     lib.ppn_resize_ce_fwd.argtypes = [_p, _p, _p, _p, _p, _p, C.c_int64] + [C.c_int] * 9 + [_p]
     lib.ppn_resize_ce_bwd.argtypes = [_p, _p, _p, _p, _p] + [C.c_int] * 9 + [_p]
     lib.ppn_seg_eval.argtypes = [_p, _p, _p, _p] + [C.c_int] * 9 + [_p]
+    lib.ppn_ohem_ce_workspace.argtypes = [C.c_int] * 3
+    lib.ppn_ohem_ce_workspace.restype = C.c_int64
+    lib.ppn_ohem_ce_fwd.argtypes = [_p] * 10 + [C.c_int64] + [C.c_int] * 8 + [C.c_float] + [C.c_int] * 3 + [_p]
+    lib.ppn_ohem_ce_bwd.argtypes = [_p] * 8 + [C.c_int] * 10 + [_p]
     lib.ppn_augment_params.argtypes = [C.c_uint64, C.c_uint64, C.c_int] + [C.c_double] * 6 + [C.c_int, _p, _p]
     lib.ppn_augment_codes.argtypes = [_p, _p, _p, _p, _p] + [C.c_int] * 5 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, _p]
     lib.ppn_augment_rgb.argtypes = lib.ppn_augment_codes.argtypes
@@ -173,7 +178,7 @@ def _load():
     for name in EXPORTS:
         getattr(lib, name)
         if name not in ("ppn_error_string", "ppn_na2d_bwd_workspace", "ppn_na2d_bwd_vpad_workspace", "ppn_mhsa_bwd_workspace", "ppn_swin_wmsa_bwd_workspace",
-                        "ppn_resize_ce_workspace"):
+                        "ppn_resize_ce_workspace", "ppn_ohem_ce_workspace"):
             getattr(lib, name).restype = C.c_int
     return lib
 

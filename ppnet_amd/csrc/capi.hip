@@ -534,6 +534,57 @@ int ppn_seg_eval(const void* logit, const void* label, uint8_t* pred, int64_t* a
     return PPN_OK;
 }
 
+int64_t ppn_ohem_ce_workspace(int B, int H, int W) {
+    if (ppn_resize_ce_workspace(B, H, W) < 0) return -1;                                               // the same limits on B, H, W
+    return ppn::ohem_ce_workspace_bytes();
+}
+
+// what both OHEM entry points check alike: sizes, dtypes, mode, and the buffers they share
+static bool ohem_ce_common_ok(const void* logit, const void* label, const float* class_weight, const float* lse, const float* score, int B, int C,
+                              int h, int w, int H, int W, int mode, int logit_dtype, int label_dtype) {
+    if (!logit || !label || !lse || !score) return false;                                              // class_weight may be NULL: all ones
+    if ((logit_dtype != 0 && logit_dtype != 1) || (label_dtype != 0 && label_dtype != 1) || mode < 0 || mode > 2) return false;
+    if ((((uintptr_t)logit | (uintptr_t)lse | (uintptr_t)score) & 15) != 0 || ((uintptr_t)class_weight & 3) != 0) return false;
+    if (label_dtype == 1 && ((uintptr_t)label & 7) != 0) return false;
+    return resize_ce_sizes_ok(B, C, h, w, H, W);
+}
+
+int ppn_ohem_ce_fwd(const void* logit, const void* label, const float* class_weight, float* lse, float* score, float* loss, int64_t* counts,
+                    float* threshold, uint8_t* mask, void* workspace, int64_t workspace_bytes, int B, int C, int h, int w, int H, int W,
+                    int ignore_index, int mode, float thresh, int min_kept, int logit_dtype, int label_dtype, void* stream) {
+    if (!loss || !counts || !threshold || !workspace) return PPN_E_INVALID;                            // mask may be NULL: not wanted
+    if (!ohem_ce_common_ok(logit, label, class_weight, lse, score, B, C, h, w, H, W, mode, logit_dtype, label_dtype)) return PPN_E_INVALID;
+    if (((uintptr_t)workspace & 15) != 0 || (((uintptr_t)loss | (uintptr_t)threshold) & 3) != 0 || ((uintptr_t)counts & 7) != 0) return PPN_E_INVALID;
+    if (mode != 0 && min_kept < 1) return PPN_E_INVALID;
+    if (mode == 1 && !(thresh > 0.0f && thresh <= 1.0f)) return PPN_E_INVALID;                         // NaN included
+    const long long n_px = (long long)B * H * W, px = ppn::ohem_ce_pixels(), tiles = (n_px + px - 1) / px;
+    const long long groups = tiles < ppn::ohem_ce_max_groups() ? tiles : ppn::ohem_ce_max_groups();
+    if (tiles >= 0x7fffffffLL || groups * ppn::ohem_ce_threads() >= 0x7fffffffLL) return PPN_E_INVALID;
+    const int64_t need = ppn_ohem_ce_workspace(B, H, W);
+    if (need < 0 || workspace_bytes < need) return PPN_E_INVALID;
+    // batch_kept = min_kept * B, capped at the pixel count (beyond n_valid every value means the same)
+    const long long kept = mode == 0 ? n_px : ((long long)min_kept * B < n_px ? (long long)min_kept * B : n_px);
+    const int e = ppn::ohem_ce_fwd_launch(logit, label, class_weight, lse, score, loss, counts, threshold, mask, workspace, B, C, h, w, H, W,
+                                          ignore_index, mode, thresh, (uint32_t)kept, logit_dtype, label_dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_ohem_ce_bwd(const void* logit, const void* label, const float* class_weight, const float* lse, const float* score, const float* threshold,
+                    const float* grad_out, void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index, int mode, int logit_dtype,
+                    int label_dtype, void* stream) {
+    if (!threshold || !grad_out || !dlogit) return PPN_E_INVALID;
+    if (!ohem_ce_common_ok(logit, label, class_weight, lse, score, B, C, h, w, H, W, mode, logit_dtype, label_dtype)) return PPN_E_INVALID;
+    if (((uintptr_t)dlogit & 15) != 0 || (((uintptr_t)threshold | (uintptr_t)grad_out) & 3) != 0) return PPN_E_INVALID;
+    // work-items of the launch: 1, 8 or 64 lanes per dlogit element in whole workgroups
+    const long long per = ppn::ohem_ce_threads() / ppn::resize_ce_bwd_lanes(h, w, H, W);
+    if ((((long long)B * C * h * w + per - 1) / per) * ppn::ohem_ce_threads() >= 0x7fffffffLL) return PPN_E_INVALID;
+    const int e = ppn::ohem_ce_bwd_launch(logit, label, class_weight, lse, score, threshold, grad_out, dlogit, B, C, h, w, H, W, ignore_index, mode,
+                                          logit_dtype, label_dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_residual_layernorm(const void* x, const void* a, const void* gamma, const void* w, const void* b, void* x_out,
                            void* y_out, int64_t rows, int32_t C, float eps, int32_t dtype, void* stream) {
     return ppn_residual_layernorm_padded(x, a, gamma, w, b, x_out, y_out, rows, C, eps, dtype, 0, 0, 0, 0, stream);

@@ -177,6 +177,19 @@ int seg_eval_max_groups();
 int seg_eval_max_classes();
 int seg_eval_launch(const void* logit, const void* label, uint8_t* pred, int64_t* areas, int B, int C, int h, int w, int H, int W, int ignore_index,
                     int logit_dtype, int label_dtype, hipStream_t stream);
+// ohem_ce.hip: resize_ce.hip's loss with online hard example mining (a radix select of the k-th score) and class weights, forward and
+// backward; pixels per tile, work-items per workgroup, the largest grid (a workgroup strides over the tiles) and the workspace (bytes,
+// the same for every size).  mode 0 = no sampler, 1 = threshold on the label's probability, 2 = the batch_kept largest losses
+int ohem_ce_pixels();
+int ohem_ce_threads();
+int ohem_ce_max_groups();
+long long ohem_ce_workspace_bytes();
+int ohem_ce_fwd_launch(const void* logit, const void* label, const float* class_weight, float* lse, float* score, float* loss, int64_t* counts,
+                       float* threshold, uint8_t* mask, void* workspace, int B, int C, int h, int w, int H, int W, int ignore_index, int mode,
+                       float thresh, uint32_t batch_kept, int logit_dtype, int label_dtype, hipStream_t stream);
+int ohem_ce_bwd_launch(const void* logit, const void* label, const float* class_weight, const float* lse, const float* score, const float* threshold,
+                       const float* grad_out, void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index, int mode, int logit_dtype,
+                       int label_dtype, hipStream_t stream);
 // augment.hip: SegNet's training input (flip + photometric distortion + normalise + pad) from occupancy codes or u8 RGB images;
 // work-items per workgroup and output pixels per workgroup (a workgroup serves one image)
 int augment_threads();

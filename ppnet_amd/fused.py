@@ -892,3 +892,117 @@ def seg_eval(logit, labels, ignore_index=255, want_pred=False):
     L.check(rc, "ppn_seg_eval")
     EVAL_CALLS["fwd"] += 1
     return areas, pred
+
+
+# ---------------------------------------------------------------- the heads' training loss with a pixel sampler and class weights
+OHEM_CALLS = {"fwd": 0, "bwd": 0}        # launches of ppn_ohem_ce_fwd / ppn_ohem_ce_bwd (like LOSS_CALLS, which they leave alone)
+OHEM_THREADS = 256                       # work-items per workgroup of every kernel of csrc/ohem_ce.hip
+OHEM_PIXELS = 1024                       # pixels per tile
+OHEM_MAX_GROUPS = 1024                   # workgroups at most: beyond OHEM_MAX_GROUPS tiles a workgroup strides over several
+OHEM_DIGIT_BITS = (11, 11, 10)           # the radix select's three digits of the 32-bit score key
+OHEM_MODE_NONE, OHEM_MODE_THRESH, OHEM_MODE_TOPK = 0, 1, 2
+
+
+def ohem_ce_ok(logit, labels):
+    """Whether ppn_ohem_ce_fwd / _bwd take these tensors: ppn_resize_ce_fwd's types and limits (the backward launches the same grid)."""
+    return resize_ce_ok(logit, labels)
+
+
+def _ohem_mode(thresh, min_kept):
+    """(mode, thresh, min_kept) of the entry points: no sampler without min_kept, else the threshold or the top-k form."""
+    if min_kept is None:
+        if thresh is not None:
+            raise ValueError("ohem_cross_entropy: thresh without min_kept (a sampler has both; min_kept=None means no sampler)")
+        return OHEM_MODE_NONE, 1.0, 1
+    return (OHEM_MODE_TOPK, 1.0, int(min_kept)) if thresh is None else (OHEM_MODE_THRESH, float(thresh), int(min_kept))
+
+
+def _ohem_ce_fwd(logit, labels, cw, ignore_index, mode, thresh, min_kept, want_mask):
+    """One ppn_ohem_ce_fwd on contiguous tensors: (loss 0-d float32, counts int64 [3], threshold 0-d float32, lse, score [B,H,W]
+    float32, mask uint8 [B,H,W] or None), all on the device."""
+    B, C, h, w = logit.shape
+    H, W = labels.shape[-2:]
+    dev = logit.device
+    need = L.lib.ppn_ohem_ce_workspace(B, H, W)
+    if need < 0:
+        raise L.PpnError(f"ppn_ohem_ce_workspace: invalid sizes B={B} H={H} W={W}", -1)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    threshold = torch.empty((), dtype=torch.float32, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    lse = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    score = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    mask = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if want_mask else None
+    with torch.cuda.device(dev):
+        rc = L.lib.ppn_ohem_ce_fwd(_p(logit), _p(labels), _p(cw), _p(lse), _p(score), _p(loss), _p(counts), _p(threshold), _p(mask), _p(ws), need,
+                                   B, C, h, w, H, W, ignore_index, mode, thresh, min_kept, _DT[logit.dtype], _LABEL_DT[labels.dtype],
+                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    L.check(rc, "ppn_ohem_ce_fwd")
+    OHEM_CALLS["fwd"] += 1
+    return loss, counts, threshold, lse, score, mask
+
+
+def _ohem_ce_bwd(logit, labels, cw, lse, score, threshold, grad_out, ignore_index, mode):
+    """One ppn_ohem_ce_bwd: dlogit in logit's layout and dtype; threshold and grad_out float32 scalars on the device."""
+    B, C, h, w = logit.shape
+    H, W = labels.shape[-2:]
+    dlogit = torch.empty_like(logit)
+    with torch.cuda.device(logit.device):
+        rc = L.lib.ppn_ohem_ce_bwd(_p(logit), _p(labels), _p(cw), _p(lse), _p(score), _p(threshold), _p(grad_out), _p(dlogit), B, C, h, w, H, W,
+                                   ignore_index, mode, _DT[logit.dtype], _LABEL_DT[labels.dtype],
+                                   ctypes.c_void_p(torch.cuda.current_stream(logit.device).cuda_stream))
+    L.check(rc, "ppn_ohem_ce_bwd")
+    OHEM_CALLS["bwd"] += 1
+    return dlogit
+
+
+class _OhemCEFunction(torch.autograd.Function):
+    """Saves logit, labels, the class weights, the per-pixel log-sum-exp and score, and the device threshold; no weight tensor."""
+
+    @staticmethod
+    def forward(ctx, logit, labels, cw, ignore_index, mode, thresh, min_kept, want_mask):
+        loss, counts, threshold, lse, score, mask = _ohem_ce_fwd(logit, labels, cw, ignore_index, mode, thresh, min_kept, want_mask)
+        ctx.save_for_backward(logit, labels, lse, score, threshold, *(() if cw is None else (cw,)))
+        ctx.ignore_index, ctx.mode = ignore_index, mode
+        out = (loss, counts) if mask is None else (loss, counts, mask)
+        ctx.mark_non_differentiable(*out[1:])
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_loss, *_unused):
+        logit, labels, lse, score, threshold, *cw = ctx.saved_tensors
+        g = grad_loss.to(dtype=torch.float32, device=logit.device).contiguous()          # stays on the device: no synchronisation
+        d = _ohem_ce_bwd(logit, labels, cw[0] if cw else None, lse, score, threshold, g, ctx.ignore_index, ctx.mode)
+        return d, None, None, None, None, None, None, None
+
+
+def ohem_cross_entropy(logit, labels, ignore_index=255, class_weight=None, thresh=None, min_kept=None, want_mask=False):
+    """(loss, correct, n_kept[, mask]) of a head's low-resolution logits [B,C,h,w] (float32 / bfloat16) against labels [B,H,W] (uint8 /
+    int64) under mmseg's OHEMPixelSampler(thresh, min_kept) and CrossEntropyLoss(class_weight): loss = the sum over the SELECTED
+    pixels of class_weight[label] * cross-entropy of the logits resized bilinearly (align_corners=False) to H x W, divided by ALL B*H*W
+    pixels — a 0-d float32 tensor differentiable w.r.t. `logit`; correct = valid pixels whose argmax equals the label (sampling does not
+    change it) and n_kept = selected pixels, 0-d int64; mask uint8 [B,H,W] (1 selected) with want_mask.  min_kept=None: no sampler,
+    every valid pixel (class weights only); thresh given: pixels whose label probability is below max(thresh, the
+    min(min_kept * B, n_valid - 1)-th smallest one); thresh=None: the min_kept * B largest losses, ties at the cut all kept.  class_weight:
+    a float32 tensor [C] on the logits' device, or None.  Neither the resized logits nor a weight tensor is built and nothing is read
+    back (ppn_ohem_ce_fwd / ppn_ohem_ce_bwd); a label outside [0, C) counts as ignored."""
+    if not (logit.is_cuda and labels.is_cuda):
+        raise RuntimeError("ppnet_amd.fused: GPU tensors only (no CPU fallback)")
+    if not ohem_ce_ok(logit, labels):
+        raise ValueError(f"ohem_cross_entropy: logits {tuple(logit.shape)} {logit.dtype} / labels {tuple(labels.shape)} {labels.dtype} "
+                         "are outside ppn_ohem_ce_fwd's types and limits")
+    mode, thresh, min_kept = _ohem_mode(thresh, min_kept)
+    if min_kept < 1 or (mode == OHEM_MODE_THRESH and not 0.0 < thresh <= 1.0):
+        raise ValueError(f"ohem_cross_entropy: min_kept {min_kept} / thresh {thresh} outside min_kept >= 1, 0 < thresh <= 1")
+    cw = None
+    if class_weight is not None:
+        cw = torch.as_tensor(class_weight, dtype=torch.float32, device=logit.device).contiguous()
+        if cw.shape != (logit.shape[1],):
+            raise ValueError(f"ohem_cross_entropy: class_weight {tuple(cw.shape)} for {logit.shape[1]} classes")
+    logit, labels = logit.contiguous(), labels.contiguous()
+    if torch.is_grad_enabled() and logit.requires_grad:
+        loss, counts, *mask = _OhemCEFunction.apply(logit, labels, cw, int(ignore_index), mode, thresh, min_kept, bool(want_mask))
+    else:
+        loss, counts, _, _, _, m = _ohem_ce_fwd(logit.detach(), labels, cw, int(ignore_index), mode, thresh, min_kept, bool(want_mask))
+        mask = [] if m is None else [m]
+    return (loss, counts[0], counts[2], *mask)

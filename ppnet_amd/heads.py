@@ -67,12 +67,52 @@ def _in_equal_slices(feats, bmax, run):
     return torch.cat([run([t[i:i + step] if t is not None else None for t in feats]) for i in range(0, B, step)], dim=0)
 
 
+class OHEMPixelSampler:
+    """mmseg's online hard example mining sampler (core/seg/sampler/ohem_pixel_sampler.py:11-30): `thresh` — pixels whose label
+    probability is below it are hard; None: the min_kept largest losses — and `min_kept`, the pixels kept at least, PER IMAGE (the
+    sampler multiplies by the batch size).  It only holds the two numbers: ohem_weight is its sample(), and on the GPU
+    resized_decode_losses hands them to the fused kernels (fused.ohem_cross_entropy)."""
+
+    def __init__(self, context=None, thresh=None, min_kept=100000):
+        assert min_kept > 1
+        self.context, self.thresh, self.min_kept = context, thresh, min_kept
+
+    def __repr__(self):
+        return f"OHEMPixelSampler(thresh={self.thresh}, min_kept={self.min_kept})"
+
+
+def _loss_options(sampler, loss_decode, num_classes):
+    """(sampler, class_weight) of a head from the reference's config entries `sampler=dict(type='OHEMPixelSampler', thresh=...,
+    min_kept=...)` (decode_head.py:96-99) and `loss_decode=dict(type='CrossEntropyLoss', class_weight=[...])`
+    (losses/cross_entropy_loss.py:158-171): an OHEMPixelSampler or None, and a tuple of num_classes floats or None.  Both are kept as
+    plain attributes of the head — no buffer, so no checkpoint key.  Another sampler type, or class weights given as a file path
+    (losses/utils.py:9-24), raise NotImplementedError."""
+    if isinstance(sampler, dict):
+        cfg = dict(sampler)
+        typ = cfg.pop("type", None)
+        if typ != "OHEMPixelSampler":
+            raise NotImplementedError(f"pixel sampler type {typ!r}: OHEMPixelSampler only")
+        sampler = OHEMPixelSampler(**cfg)
+    elif sampler is not None and not isinstance(sampler, OHEMPixelSampler):
+        raise NotImplementedError(f"pixel sampler {sampler!r}: a dict(type='OHEMPixelSampler', ...) or an OHEMPixelSampler")
+    cw = loss_decode.get("class_weight") if isinstance(loss_decode, dict) else None
+    if cw is not None:
+        if isinstance(cw, str):
+            raise NotImplementedError(f"class_weight {cw!r}: a list of {num_classes} floats (files are not read)")
+        cw = tuple(float(v) for v in cw)
+        if len(cw) != num_classes:
+            raise ValueError(f"class_weight has {len(cw)} entries for {num_classes} classes")
+    return sampler, cw
+
+
 class SETRUPHead(nn.Module):
     def __init__(self, in_channels=1024, channels=512, num_classes=2, num_convs=1, up_scale=4, kernel_size=3,
-                 in_index=-1, dropout_ratio=0.1, align_corners=False, norm_layer=None, norm_cfg=None, **kwargs):
+                 in_index=-1, dropout_ratio=0.1, align_corners=False, norm_layer=None, norm_cfg=None, sampler=None, loss_decode=None,
+                 **kwargs):
         super().__init__()
         assert kernel_size in (1, 3)
         self.in_index, self.align_corners = in_index, align_corners
+        self.sampler, self.class_weight = _loss_options(sampler, loss_decode, num_classes)
         self.norm = nn.LayerNorm(in_channels, eps=1e-6)
         self.up_convs = nn.ModuleList()
         cin = in_channels
@@ -147,9 +187,10 @@ class UPerHead(nn.Module):
     (SegNet/test.py:29-32 -> configs/nat/upernet_nat_base.py)."""
 
     def __init__(self, in_channels=(128, 256, 512, 1024), channels=64, num_classes=2, pool_scales=(1, 2, 3, 6),
-                 in_index=(0, 1, 2, 3), dropout_ratio=0.1, align_corners=False, norm_cfg=None, **kwargs):
+                 in_index=(0, 1, 2, 3), dropout_ratio=0.1, align_corners=False, norm_cfg=None, sampler=None, loss_decode=None, **kwargs):
         super().__init__()
         self.in_index, self.align_corners = tuple(in_index), align_corners
+        self.sampler, self.class_weight = _loss_options(sampler, loss_decode, num_classes)
         self.psp_modules = nn.ModuleList(
             nn.Sequential(nn.AdaptiveAvgPool2d(ps), _ConvModule(in_channels[-1], channels, 1)) for ps in pool_scales)
         self.bottleneck = _ConvModule(in_channels[-1] + len(pool_scales) * channels, channels, 3)
@@ -293,10 +334,12 @@ class UPerPUPHead(UPerHead):
     torch.cat does.  The head of configs/nat/dense_nat_base.py and configs/swin/dense_swin_base.py."""
 
     def __init__(self, in_channels=(128, 256, 512, 1024), channels=256, num_classes=2, num_convs=(2, 3, 4, 5), up_scale=2,
-                 pool_scales=(1, 2, 3, 6), in_index=(0, 1, 2, 3), dropout_ratio=0.1, align_corners=False, norm_cfg=None, **kwargs):
+                 pool_scales=(1, 2, 3, 6), in_index=(0, 1, 2, 3), dropout_ratio=0.1, align_corners=False, norm_cfg=None, sampler=None,
+                 loss_decode=None, **kwargs):
         nn.Module.__init__(self)
         assert len(num_convs) == len(in_channels) == len(in_index)
         self.in_index, self.align_corners, self.num_convs = tuple(in_index), align_corners, tuple(num_convs)
+        self.sampler, self.class_weight = _loss_options(sampler, loss_decode, num_classes)
         # registration order = mmseg's state-dict order (BaseDecodeHead.__init__ makes conv_seg and dropout first, decode_head.py:102-106)
         self.conv_seg = nn.Conv2d(channels, num_classes, 1)
         self.dropout = nn.Dropout2d(dropout_ratio) if dropout_ratio > 0 else nn.Identity()
@@ -398,11 +441,12 @@ class FCNHead(nn.Module):
     `convs.i.{conv,bn}`, `conv_cat.{conv,bn}`, `conv_seg`.  Training only: inference never evaluates it (encoder_decoder.py:63-80)."""
 
     def __init__(self, in_channels=256, channels=256, num_classes=19, num_convs=2, kernel_size=3, concat_input=True, dilation=1,
-                 in_index=-1, dropout_ratio=0.1, align_corners=False, norm_cfg=None, loss_decode=None, **kwargs):
+                 in_index=-1, dropout_ratio=0.1, align_corners=False, norm_cfg=None, loss_decode=None, sampler=None, **kwargs):
         super().__init__()
         assert num_convs >= 0 and dilation > 0
         self.in_index, self.align_corners, self.concat_input = in_index, align_corners, concat_input
         self.loss_weight = float((loss_decode or {}).get("loss_weight", 1.0))
+        self.sampler, self.class_weight = _loss_options(sampler, loss_decode, num_classes)
         if num_convs == 0:
             assert in_channels == channels
             self.convs = nn.Identity()
@@ -422,28 +466,100 @@ class FCNHead(nn.Module):
         return self.conv_seg(self.dropout(y))
 
 
-def decode_losses(logit, gt, loss_weight=1.0, ignore_index=255):
+def _valid_labels(gt, num_classes, ignore_index):
+    return (gt != ignore_index) & (gt >= 0) & (gt < num_classes)
+
+
+_CLASS_WEIGHTS = {}        # (weights, device, dtype) -> tensor: a head's list goes to the device once, not every step
+
+
+def _class_weight_tensor(class_weight, device, dtype):
+    if class_weight is None or torch.is_tensor(class_weight):
+        return class_weight if class_weight is None else class_weight.to(device=device, dtype=dtype)
+    key = (tuple(float(v) for v in class_weight), device, dtype)
+    if key not in _CLASS_WEIGHTS:
+        _CLASS_WEIGHTS[key] = torch.tensor(key[0], dtype=dtype, device=device)
+    return _CLASS_WEIGHTS[key]
+
+
+def _weighted_ce(logit, gt, class_weight, ignore_index):
+    """class_weight[label] * cross-entropy per pixel [B,H,W], 0 on ignored pixels (label == ignore_index or outside [0, C))."""
+    valid = _valid_labels(gt, logit.shape[1], ignore_index)
+    safe = torch.where(valid, gt, torch.zeros_like(gt))
+    ce = F.cross_entropy(logit, safe, weight=_class_weight_tensor(class_weight, logit.device, logit.dtype), reduction="none")
+    return ce * valid.to(ce.dtype), valid
+
+
+def ohem_weight(logit_fullres, gt, sampler, class_weight=None, ignore_index=255):
+    """OHEMPixelSampler.sample (core/seg/sampler/ohem_pixel_sampler.py:32-85) as a torch composition: the 0 / 1 weight [B,H,W], in the
+    logits' dtype, of full-resolution logits [B,C,H,W] against labels [B,H,W]; any dtype, CPU or GPU.  With n_valid valid pixels and
+    batch_kept = min_kept * B: `thresh` given — 1 where the label's softmax probability is below max(thresh, the min(batch_kept,
+    n_valid - 1)-th smallest one); thresh None — 1 on the batch_kept largest class_weight[label] * cross-entropy, and on every
+    pixel that TIES with the smallest of them (the reference's unstable sort picks among ties; keeping all is the deterministic
+    reading and the one deliberate difference); sampler None — 1 on every valid pixel.  A label outside [0, C) is ignored, the
+    build's rule."""
+    with torch.no_grad():
+        gt = gt.long()
+        valid = _valid_labels(gt, logit_fullres.shape[1], ignore_index)
+        weight = torch.zeros(gt.shape, dtype=logit_fullres.dtype, device=logit_fullres.device)
+        n_valid = int(valid.sum())
+        if sampler is None or n_valid == 0:
+            if sampler is None:
+                weight[valid] = 1.0
+            return weight
+        batch_kept = sampler.min_kept * gt.shape[0]
+        if sampler.thresh is not None:
+            safe = torch.where(valid, gt, torch.zeros_like(gt))
+            prob = F.softmax(logit_fullres, dim=1).gather(1, safe.unsqueeze(1)).squeeze(1)
+            sort_prob = prob[valid].sort().values
+            threshold = max(float(sort_prob[min(batch_kept, n_valid - 1)]), sampler.thresh)
+            weight[valid & (prob < threshold)] = 1.0
+        else:
+            score, _ = _weighted_ce(logit_fullres, gt, class_weight, ignore_index)
+            cut = score[valid].sort(descending=True).values[min(batch_kept, n_valid) - 1]
+            weight[valid & (score >= cut)] = 1.0
+        return weight
+
+
+def decode_losses(logit, gt, loss_weight=1.0, ignore_index=255, class_weight=None, sampler=None):
     """(loss_ce, acc_seg) of BaseDecodeHead.losses (decode_head.py:231-265) for resized logits [B,C,H,W] and labels [B,H,W].
     mmseg's CrossEntropyLoss is F.cross_entropy(reduction='none', ignore_index) followed by a mean over ALL pixels — ignored
     ones contribute 0 to the sum and still count in the divisor (losses/cross_entropy_loss.py:20-31, losses/utils.py:66-68);
-    accuracy() is called without an ignore index and divides by target.numel() (decode_head.py:264, losses/accuracy.py:39-49)."""
-    loss = loss_weight * F.cross_entropy(logit, gt, ignore_index=ignore_index, reduction="none").mean()
+    accuracy() is called without an ignore index and divides by target.numel() (decode_head.py:264, losses/accuracy.py:39-49).
+    class_weight (C floats or a tensor) scales every pixel's term by its label's weight and sampler (an OHEMPixelSampler) by
+    ohem_weight's 0 / 1, still under the mean over all pixels (decode_head.py:245-256); acc_seg is not changed by either.  With
+    both None this is the two library calls it always was."""
+    if class_weight is None and sampler is None:
+        loss = loss_weight * F.cross_entropy(logit, gt, ignore_index=ignore_index, reduction="none").mean()
+    else:
+        ce, _ = _weighted_ce(logit, gt, class_weight, ignore_index)
+        loss = loss_weight * (ce * ohem_weight(logit, gt, sampler, class_weight, ignore_index).to(ce.dtype)).mean()
     with torch.no_grad():
         acc = (logit.argmax(1) == gt).float().sum() * (100.0 / gt.numel())
     return loss, acc
 
 
-def resized_decode_losses(logit_lowres, gt, loss_weight=1.0, ignore_index=255, align_corners=False):
+def resized_decode_losses(logit_lowres, gt, loss_weight=1.0, ignore_index=255, align_corners=False, class_weight=None, sampler=None):
     """decode_losses of a head's LOW-resolution logits [B,C,h,w] resized bilinearly to the labels' size [B,H,W]: the same
     (loss_ce, acc_seg).  CUDA float32 / bfloat16 logits with CUDA uint8 / int64 labels, align_corners False and sizes inside
     ppn_resize_ce_fwd's limits run on the fused kernel pair (fused.resize_cross_entropy: the resized logits are never built, the
-    gradient reaches the low-resolution logits directly); PPNET_LIBRARY_LOSS=1 (read at call time), CPU tensors and everything else
-    take the library composition, F.interpolate of the float32 logits followed by decode_losses on int64 labels."""
-    if not align_corners and not os.environ.get("PPNET_LIBRARY_LOSS") and fused.resize_ce_ok(logit_lowres, gt):
-        mean, correct = fused.resize_cross_entropy(logit_lowres, gt, ignore_index)
-        return loss_weight * mean, correct.float() * (100.0 / gt.numel())        # (a count below 2^24 is exact in float32)
+    gradient reaches the low-resolution logits directly) — with class_weight or sampler on fused.ohem_cross_entropy's kernels
+    (ppn_ohem_ce_fwd / _bwd: the sampler is a radix select on the device, no sort, no weight tensor; a thresh outside (0, 1] is
+    outside them); PPNET_LIBRARY_LOSS=1 (read at call time), CPU tensors and everything else take the library composition,
+    F.interpolate of the float32 logits followed by decode_losses on int64 labels."""
+    own = not align_corners and not os.environ.get("PPNET_LIBRARY_LOSS")
+    if class_weight is None and sampler is None:
+        if own and fused.resize_ce_ok(logit_lowres, gt):
+            mean, correct = fused.resize_cross_entropy(logit_lowres, gt, ignore_index)
+            return loss_weight * mean, correct.float() * (100.0 / gt.numel())        # (a count below 2^24 is exact in float32)
+    elif (own and fused.ohem_ce_ok(logit_lowres, gt)
+          and (sampler is None or sampler.thresh is None or 0.0 < sampler.thresh <= 1.0)):
+        cw = _class_weight_tensor(class_weight, logit_lowres.device, torch.float32)
+        mean, correct, _ = fused.ohem_cross_entropy(logit_lowres, gt, ignore_index, cw, None if sampler is None else sampler.thresh,
+                                                    None if sampler is None else sampler.min_kept)
+        return loss_weight * mean, correct.float() * (100.0 / gt.numel())
     logit = F.interpolate(logit_lowres.float(), gt.shape[-2:], mode="bilinear", align_corners=align_corners)
-    return decode_losses(logit, gt.long(), loss_weight, ignore_index)
+    return decode_losses(logit, gt.long(), loss_weight, ignore_index, class_weight, sampler)
 
 
 def eval_areas(pred, gt, num_classes, ignore_index=255):

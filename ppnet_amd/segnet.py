@@ -16,7 +16,7 @@ from .dense import (IMG_MEAN, IMG_STD, LIBRARY_GEMM_BELOW_C, LIBRARY_GEMM_FROM_C
 from .dense import accumulate as _accumulate, bias32 as _bias32, library_width as _library_width, linear as _linear  # noqa: F401
 from .dense import mfma_weights as _mfma_weights, own_gemm_ok as _own_gemm_ok, use_mfma_conv as _use_mfma_conv  # noqa: F401
 from .heads import FCNHead, SETRUPHead, UPerHead, UPerPUPHead, _ConvModule, _Upsample, decode_losses, resized_decode_losses  # noqa: F401
-from .heads import eval_areas, resized_eval_areas
+from .heads import OHEMPixelSampler, eval_areas, ohem_weight, resized_eval_areas  # noqa: F401
 from .na import NeighborhoodAttention2D  # noqa: F401
 from .nat import NAT, ConvDownsampler, ConvTokenizer, DiNAT, Mlp, NATBlock, NATLayer, _fold_doc  # noqa: F401
 from .swin import SwinTransformer
@@ -77,8 +77,10 @@ class SegNet(nn.Module):
         """cfg: the reference's `model = dict(type='EncoderDecoder', pretrained=..., backbone=dict(type='DiNAT', ...),
         decode_head=dict(type='SETRUPHead', ...), auxiliary_head=..., train_cfg=..., test_cfg=dict(mode='whole'))`
         (configs/_base_/models/dinat.py:3-46 merged with configs/dinat/dinat_base.py:5-24), or a whole config holding it under
-        'model'.  mmcv-only keys (init_cfg, norm_cfg, loss_decode, conv_cfg, act_cfg, in_patch_size, frozen_stages) are accepted
-        and ignored where this build has one fixed choice."""
+        'model'.  A head's `sampler=dict(type='OHEMPixelSampler', thresh=..., min_kept=...)` and `loss_decode['class_weight']` (a list
+        of floats) are read and applied by forward_train (heads._loss_options; another sampler type or a weight file raises);
+        `loss_decode['loss_weight']` is read by the auxiliary head.  mmcv-only keys (init_cfg, norm_cfg, conv_cfg, act_cfg,
+        in_patch_size, frozen_stages, the rest of loss_decode) are accepted and ignored where this build has one fixed choice."""
         cfg = dict(cfg.get("model", cfg))
         typ = cfg.pop("type", "EncoderDecoder")
         if typ != "EncoderDecoder":
@@ -189,7 +191,8 @@ class SegNet(nn.Module):
 
     def forward_train(self, img, img_metas, gt_semantic_seg, **kwargs):
         """encoder_decoder.py:122-152 with decode_head.py:209-237 (losses): {'decode.loss_ce', 'decode.acc_seg'} and, with an
-        auxiliary head, {'aux.loss_ce', 'aux.acc_seg'} (loss weights 1.0 / 0.4, ignore_index 255)."""
+        auxiliary head, {'aux.loss_ce', 'aux.acc_seg'} (loss weights 1.0 / 0.4, ignore_index 255).  Each head's own pixel sampler and
+        class weights (decode_head.py:245-256) go with its logits."""
         if self.prepared:
             raise RuntimeError("SegNet.prepare_inference() folded BatchNorm / LayerScale into the weights: build a fresh SegNet to train")
         feats = self.backbone(img)
@@ -201,7 +204,8 @@ class SegNet(nn.Module):
                                                        for i, h in enumerate(self._aux_heads())]
         for name, head, w in heads:
             # the head's output in its own dtype: the resize and the loss are one kernel pair on the GPU (heads.resized_decode_losses)
-            losses[f"{name}.loss_ce"], losses[f"{name}.acc_seg"] = resized_decode_losses(head(feats), gt, w, align_corners=head.align_corners)
+            losses[f"{name}.loss_ce"], losses[f"{name}.acc_seg"] = resized_decode_losses(
+                head(feats), gt, w, align_corners=head.align_corners, class_weight=head.class_weight, sampler=head.sampler)
         return losses
 
     @torch.no_grad()
