@@ -70,7 +70,7 @@ extern "C" {
  * 111 = ppn_na2d_bwd_vpad, ppn_na2d_bwd_vpad_workspace.  ppn_resize_ce_workspace, ppn_resize_ce_fwd and ppn_resize_ce_bwd joined at
  * 111 too, and so did ppn_seg_eval and ppn_augment_params / ppn_augment_codes / ppn_augment_rgb: new symbols change no existing
  * argument list and remove nothing, which is all the version guards against.  ppn_ohem_ce_workspace, ppn_ohem_ce_fwd and
- * ppn_ohem_ce_bwd joined at 111 in the same way. */
+ * ppn_ohem_ce_bwd joined at 111 in the same way, and so did ppn_resize_dice_workspace, ppn_resize_dice_fwd and ppn_resize_dice_bwd. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -436,6 +436,38 @@ int ppn_ohem_ce_fwd(const void* logit, const void* label, const float* class_wei
 int ppn_ohem_ce_bwd(const void* logit, const void* label, const float* class_weight, const float* lse, const float* score,
                     const float* threshold /* device, 1 */, const float* grad_out /* device, 1 */, void* dlogit,
                     int B, int C, int h, int w, int H, int W, int ignore_index, int mode, int logit_dtype, int label_dtype, void* stream);
+
+/* mmseg's DiceLoss (models/losses/dice_loss.py, exponent 2) of a segmentation head without the resized logits, their softmax or a
+ * one-hot tensor: logit [B][C][h][w] resized bilinearly to H x W with ppn_resize_ce_fwd's own tap arithmetic (the same interpolated
+ * logits bit for bit), per pixel p_i = exp(z_i - lse), v = the label is valid (not ignore_index and inside [0, C)), tc = the label
+ * clamped into [0, C - 1], and per image and class
+ *   I = sum_px p_i [tc == i] v,   P2 = sum_px p_i^2,   T = #{px: tc == i}  (not masked: the reference's denominator counts an ignored
+ *   label as the class its clamp lands on),   N = 2 I + smooth,   Den = P2 + T + smooth,
+ *   *loss = 1 / (C B) sum_b sum_{i != ignore_index} cw_i (1 - N / Den)       (cw = class_weight [C] float32 on the device, NULL = ones;
+ *   the loss's own loss_weight stays with the caller).  sums [B][C][3] float64 = I | P2 | T (T an exact integer), WRITTEN; *correct =
+ * valid pixels whose argmax (ties to the lowest class) equals the label, ppn_resize_ce_fwd's count; lse [B][H][W] float32, when not
+ * NULL, is WRITTEN for every pixel and is the only per-pixel state the backward reads.  A label never indexes memory.
+ * ppn_resize_dice_bwd: dlogit[b][c][y][x] = the sum over the pixels (Y, X) whose taps touch (y, x) of wy wx p_c (g_c - s), g_i =
+ * a[b][i] [tc == i] v + b[b][i] p_i, s = sum_i g_i p_i, a = -2 k_i / Den, b = 2 k_i N / Den^2, k_i = *grad_out cw_i / (C B), 0 for
+ * i == ignore_index — the coefficients are derived on the device from sums, smooth, class_weight and *grad_out (nothing is read back);
+ * a first pass writes s, one float32 per pixel, into the workspace, then ppn_resize_ce_bwd's gather: one writer per element, dlogit
+ * fully WRITTEN.  Same class_weight, smooth and ignore_index as the forward.  No atomics anywhere and every sum has a fixed order
+ * (per-tile partials in a fixed tree, then in double): sums, loss, correct and dlogit are bitwise reproducible.
+ * workspace: ppn_resize_dice_workspace(B, C, H, W) = 4 * max(B * ceil(H W / 1024) * (3 C + 1), B H W + 4 B C) BYTES, 16-byte aligned,
+ * needs NO initialisation; both calls use it from its start (the backward overwrites what the forward left).  float32 arithmetic
+ * for both logit dtypes (0 = float32, 1 = bfloat16: widened on load, dlogit rounded once); label_dtype 0 = uint8, 1 = int64.  NULL
+ * pointers (class_weight, and lse in the forward, excepted), logit / dlogit / lse / workspace not 16-byte aligned, the others not
+ * naturally aligned, an extent <= 0, C > 256, B C h w or B H W >= 2^31, a launch of 2^31 work-items or more, a dtype other than 0 / 1
+ * and smooth negative, NaN or infinite return PPN_E_INVALID before any HIP call. */
+int64_t ppn_resize_dice_workspace(int B, int C, int H, int W);  /* bytes; < 0 for invalid sizes */
+int ppn_resize_dice_fwd(const void* logit, const void* label, const float* class_weight /* [C] device, may be NULL */, void* workspace,
+                        float* lse /* [B][H][W], may be NULL */, double* sums /* [B][C][3]: I | P2 | T */, float* loss /* 1 */,
+                        int64_t* correct /* 1 */, int B, int C, int h, int w, int H, int W, int ignore_index, float smooth,
+                        int logit_dtype /* 0 f32, 1 bf16 */, int label_dtype /* 0 u8, 1 i64 */, void* stream);
+int ppn_resize_dice_bwd(const void* logit, const void* label, const float* lse, const double* sums, const float* class_weight,
+                        const float* grad_out /* device, 1 */, void* workspace, void* dlogit,
+                        int B, int C, int h, int w, int H, int W, int ignore_index, float smooth,
+                        int logit_dtype, int label_dtype, void* stream);
 
 /* Backward of ppn_na2d_fwd (the gradient NATTEN's natten2dqkrpb / natten2dav backward kernels compute; first brick of the
  * training step, GenNet/train.py:93-147, SegNet/mmseg/apis/train.py:67-167).  qkv [B][H][W][3][heads][32] and rpb as in the

@@ -58,7 +58,8 @@ EXPORTS = ("ppn_version", "ppn_error_string", "ppn_last_hip_error", "ppn_polyfit
            "ppn_assemble_paths", "ppn_plan_collision", "ppn_gennet_first_enc_bf16", "ppn_gennet_dec_final_bf16", "ppn_heatmap_u8", "ppn_tokenizer_conv1_codes_bf16", "ppn_tokenizer_codes_bf16", "ppn_nat128_ln_qkv_bf16", "ppn_nat128_ln_mlp_bf16", "ppn_nat128_ln_mlp_add_bf16", "ppn_nat128_proj_add_bf16",
            "ppn_resize_ce_workspace", "ppn_resize_ce_fwd", "ppn_resize_ce_bwd", "ppn_seg_eval",
            "ppn_augment_params", "ppn_augment_codes", "ppn_augment_rgb",
-           "ppn_ohem_ce_workspace", "ppn_ohem_ce_fwd", "ppn_ohem_ce_bwd")
+           "ppn_ohem_ce_workspace", "ppn_ohem_ce_fwd", "ppn_ohem_ce_bwd",
+           "ppn_resize_dice_workspace", "ppn_resize_dice_fwd", "ppn_resize_dice_bwd")
 
 
 def _load():
@@ -170,6 +171,10 @@ def _load():
     lib.ppn_ohem_ce_workspace.restype = C.c_int64
     lib.ppn_ohem_ce_fwd.argtypes = [_p] * 10 + [C.c_int64] + [C.c_int] * 8 + [C.c_float] + [C.c_int] * 3 + [_p]
     lib.ppn_ohem_ce_bwd.argtypes = [_p] * 8 + [C.c_int] * 10 + [_p]
+    lib.ppn_resize_dice_workspace.argtypes = [C.c_int] * 4
+    lib.ppn_resize_dice_workspace.restype = C.c_int64
+    lib.ppn_resize_dice_fwd.argtypes = [_p] * 8 + [C.c_int] * 7 + [C.c_float] + [C.c_int] * 2 + [_p]
+    lib.ppn_resize_dice_bwd.argtypes = [_p] * 8 + [C.c_int] * 7 + [C.c_float] + [C.c_int] * 2 + [_p]
     lib.ppn_augment_params.argtypes = [C.c_uint64, C.c_uint64, C.c_int] + [C.c_double] * 6 + [C.c_int, _p, _p]
     lib.ppn_augment_codes.argtypes = [_p, _p, _p, _p, _p] + [C.c_int] * 5 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, _p]
     lib.ppn_augment_rgb.argtypes = lib.ppn_augment_codes.argtypes
@@ -178,7 +183,7 @@ def _load():
     for name in EXPORTS:
         getattr(lib, name)
         if name not in ("ppn_error_string", "ppn_na2d_bwd_workspace", "ppn_na2d_bwd_vpad_workspace", "ppn_mhsa_bwd_workspace", "ppn_swin_wmsa_bwd_workspace",
-                        "ppn_resize_ce_workspace", "ppn_ohem_ce_workspace"):
+                        "ppn_resize_ce_workspace", "ppn_ohem_ce_workspace", "ppn_resize_dice_workspace"):
             getattr(lib, name).restype = C.c_int
     return lib
 

@@ -585,6 +585,54 @@ int ppn_ohem_ce_bwd(const void* logit, const void* label, const float* class_wei
     return PPN_OK;
 }
 
+int64_t ppn_resize_dice_workspace(int B, int C, int H, int W) {
+    if (C <= 0 || C > ppn::resize_dice_max_classes() || ppn_resize_ce_workspace(B, H, W) < 0) return -1;  // the same limits on B, H, W
+    return ppn::resize_dice_workspace_bytes(B, C, H, W);
+}
+
+// what both Dice entry points check alike: the buffers they share, dtypes, sizes, smooth
+static bool resize_dice_common_ok(const void* logit, const void* label, const float* class_weight, const void* workspace, const float* lse,
+                                  const double* sums, int B, int C, int h, int w, int H, int W, float smooth, int logit_dtype, int label_dtype) {
+    if (!logit || !label || !workspace || !sums) return false;                                         // class_weight may be NULL: all ones
+    if ((logit_dtype != 0 && logit_dtype != 1) || (label_dtype != 0 && label_dtype != 1)) return false;
+    if ((((uintptr_t)logit | (uintptr_t)workspace | (uintptr_t)lse) & 15) != 0) return false;
+    if (((uintptr_t)class_weight & 3) != 0 || ((uintptr_t)sums & 7) != 0 || (label_dtype == 1 && ((uintptr_t)label & 7) != 0)) return false;
+    if (!(smooth >= 0.0f) || smooth > 3.0e38f) return false;                                           // NaN, negative, inf
+    if (!resize_ce_sizes_ok(B, C, h, w, H, W) || C > ppn::resize_dice_max_classes()) return false;
+    // work-items of the per-pixel launches: a workgroup per tile of an image's pixels
+    const long long px = ppn::resize_dice_pixels(), tiles = (long long)B * (((long long)H * W + px - 1) / px);
+    return tiles * ppn::resize_dice_threads() < 0x7fffffffLL;
+}
+
+int ppn_resize_dice_fwd(const void* logit, const void* label, const float* class_weight, void* workspace, float* lse, double* sums, float* loss,
+                        int64_t* correct, int B, int C, int h, int w, int H, int W, int ignore_index, float smooth, int logit_dtype,
+                        int label_dtype, void* stream) {
+    if (!loss || !correct) return PPN_E_INVALID;                                                       // lse may be NULL: no backward wanted
+    if (!resize_dice_common_ok(logit, label, class_weight, workspace, lse, sums, B, C, h, w, H, W, smooth, logit_dtype, label_dtype))
+        return PPN_E_INVALID;
+    if (((uintptr_t)loss & 3) != 0 || ((uintptr_t)correct & 7) != 0) return PPN_E_INVALID;
+    const int e = ppn::resize_dice_fwd_launch(logit, label, class_weight, workspace, lse, sums, loss, correct, B, C, h, w, H, W, ignore_index, smooth,
+                                              logit_dtype, label_dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_resize_dice_bwd(const void* logit, const void* label, const float* lse, const double* sums, const float* class_weight,
+                        const float* grad_out, void* workspace, void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index,
+                        float smooth, int logit_dtype, int label_dtype, void* stream) {
+    if (!lse || !grad_out || !dlogit) return PPN_E_INVALID;
+    if (!resize_dice_common_ok(logit, label, class_weight, workspace, lse, sums, B, C, h, w, H, W, smooth, logit_dtype, label_dtype))
+        return PPN_E_INVALID;
+    if (((uintptr_t)dlogit & 15) != 0 || ((uintptr_t)grad_out & 3) != 0) return PPN_E_INVALID;
+    // work-items of the gather: 1, 8 or 64 lanes per dlogit element in whole workgroups
+    const long long per = ppn::resize_dice_threads() / ppn::resize_ce_bwd_lanes(h, w, H, W);
+    if ((((long long)B * C * h * w + per - 1) / per) * ppn::resize_dice_threads() >= 0x7fffffffLL) return PPN_E_INVALID;
+    const int e = ppn::resize_dice_bwd_launch(logit, label, lse, sums, class_weight, grad_out, workspace, dlogit, B, C, h, w, H, W, ignore_index,
+                                              smooth, logit_dtype, label_dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_residual_layernorm(const void* x, const void* a, const void* gamma, const void* w, const void* b, void* x_out,
                            void* y_out, int64_t rows, int32_t C, float eps, int32_t dtype, void* stream) {
     return ppn_residual_layernorm_padded(x, a, gamma, w, b, x_out, y_out, rows, C, eps, dtype, 0, 0, 0, 0, stream);

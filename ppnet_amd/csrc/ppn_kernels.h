@@ -190,6 +190,18 @@ int ohem_ce_fwd_launch(const void* logit, const void* label, const float* class_
 int ohem_ce_bwd_launch(const void* logit, const void* label, const float* class_weight, const float* lse, const float* score, const float* threshold,
                        const float* grad_out, void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index, int mode, int logit_dtype,
                        int label_dtype, hipStream_t stream);
+// resize_dice.hip: bilinear resize + Dice loss (mmseg's DiceLoss, exponent 2) of a segmentation head, forward and backward; pixels per
+// tile (a tile lies inside one image), work-items per workgroup, the largest C (LDS arrays are fixed) and the workspace in bytes
+int resize_dice_pixels();
+int resize_dice_threads();
+int resize_dice_max_classes();
+long long resize_dice_workspace_bytes(int B, int C, int H, int W);
+int resize_dice_fwd_launch(const void* logit, const void* label, const float* class_weight, void* workspace, float* lse, double* sums, float* loss,
+                           int64_t* correct, int B, int C, int h, int w, int H, int W, int ignore_index, float smooth, int logit_dtype,
+                           int label_dtype, hipStream_t stream);
+int resize_dice_bwd_launch(const void* logit, const void* label, const float* lse, const double* sums, const float* class_weight,
+                           const float* grad_out, void* workspace, void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index,
+                           float smooth, int logit_dtype, int label_dtype, hipStream_t stream);
 // augment.hip: SegNet's training input (flip + photometric distortion + normalise + pad) from occupancy codes or u8 RGB images;
 // work-items per workgroup and output pixels per workgroup (a workgroup serves one image)
 int augment_threads();

@@ -1006,3 +1006,115 @@ def ohem_cross_entropy(logit, labels, ignore_index=255, class_weight=None, thres
         loss, counts, _, _, _, m = _ohem_ce_fwd(logit.detach(), labels, cw, int(ignore_index), mode, thresh, min_kept, bool(want_mask))
         mask = [] if m is None else [m]
     return (loss, counts[0], counts[2], *mask)
+
+
+# ---------------------------------------------------------------- the heads' training loss: bilinear resize + Dice (mmseg's DiceLoss)
+DICE_CALLS = {"fwd": 0, "bwd": 0}        # launches of ppn_resize_dice_fwd / ppn_resize_dice_bwd (like LOSS_CALLS, which they leave alone)
+RESIZE_DICE_THREADS = 256                # work-items per workgroup of every kernel of csrc/resize_dice.hip
+RESIZE_DICE_PIXELS = 1024                # pixels per tile; a tile lies inside ONE image (the unit of ppn_resize_dice_workspace)
+RESIZE_DICE_MAX_CLASSES = 256            # the LDS partial sums and coefficients are fixed arrays
+
+
+def resize_dice_workspace_bytes(B, C, H, W):
+    """include/ppnet_hip.h's formula for ppn_resize_dice_workspace: the forward's per-tile partials or the backward's per-pixel buffer
+    and coefficients, whichever is larger, in bytes."""
+    tiles = B * -(-(H * W) // RESIZE_DICE_PIXELS)
+    return 4 * max(tiles * (3 * C + 1), B * H * W + 4 * B * C)
+
+
+def resize_dice_ok(logit, labels):
+    """Whether ppn_resize_dice_fwd / _bwd take these tensors: ppn_resize_ce_fwd's types and limits (the gather launches the same
+    grid), C <= RESIZE_DICE_MAX_CLASSES and a per-pixel launch (a workgroup per tile of an image) below 2^31 work-items."""
+    if not resize_ce_ok(logit, labels) or logit.shape[1] > RESIZE_DICE_MAX_CLASSES:
+        return False
+    B, (H, W) = labels.shape[0], labels.shape[-2:]
+    return B * -(-(H * W) // RESIZE_DICE_PIXELS) * RESIZE_DICE_THREADS < _INT32_END - 1
+
+
+def _dice_workspace(B, C, H, W, dev):
+    need = L.lib.ppn_resize_dice_workspace(B, C, H, W)
+    if need < 0:
+        raise L.PpnError(f"ppn_resize_dice_workspace: invalid sizes B={B} C={C} H={H} W={W}", -1)
+    return torch.empty(need, dtype=torch.uint8, device=dev)
+
+
+def _resize_dice_fwd(logit, labels, cw, ignore_index, smooth, want_lse):
+    """One ppn_resize_dice_fwd on contiguous tensors: (loss 0-d float32, correct 0-d int64, sums float64 [B,C,3], lse [B,H,W] float32
+    or None), all on the device."""
+    B, C, h, w = logit.shape
+    H, W = labels.shape[-2:]
+    dev = logit.device
+    ws = _dice_workspace(B, C, H, W, dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    correct = torch.empty((), dtype=torch.int64, device=dev)
+    sums = torch.empty(B, C, 3, dtype=torch.float64, device=dev)
+    lse = torch.empty(B, H, W, dtype=torch.float32, device=dev) if want_lse else None
+    with torch.cuda.device(dev):
+        rc = L.lib.ppn_resize_dice_fwd(_p(logit), _p(labels), _p(cw), _p(ws), _p(lse), _p(sums), _p(loss), _p(correct), B, C, h, w, H, W,
+                                       ignore_index, smooth, _DT[logit.dtype], _LABEL_DT[labels.dtype],
+                                       ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    L.check(rc, "ppn_resize_dice_fwd")
+    DICE_CALLS["fwd"] += 1
+    return loss, correct, sums, lse
+
+
+def _resize_dice_bwd(logit, labels, cw, lse, sums, grad_out, ignore_index, smooth):
+    """One ppn_resize_dice_bwd: dlogit in logit's layout and dtype; grad_out a float32 scalar on the device."""
+    B, C, h, w = logit.shape
+    H, W = labels.shape[-2:]
+    ws = _dice_workspace(B, C, H, W, logit.device)
+    dlogit = torch.empty_like(logit)
+    with torch.cuda.device(logit.device):
+        rc = L.lib.ppn_resize_dice_bwd(_p(logit), _p(labels), _p(lse), _p(sums), _p(cw), _p(grad_out), _p(ws), _p(dlogit), B, C, h, w, H, W,
+                                       ignore_index, smooth, _DT[logit.dtype], _LABEL_DT[labels.dtype],
+                                       ctypes.c_void_p(torch.cuda.current_stream(logit.device).cuda_stream))
+    L.check(rc, "ppn_resize_dice_bwd")
+    DICE_CALLS["bwd"] += 1
+    return dlogit
+
+
+class _ResizeDiceFunction(torch.autograd.Function):
+    """Saves logit, labels, the per-pixel log-sum-exp, the [B,C,3] sums and the class weights, nothing else."""
+
+    @staticmethod
+    def forward(ctx, logit, labels, cw, ignore_index, smooth):
+        loss, correct, sums, lse = _resize_dice_fwd(logit, labels, cw, ignore_index, smooth, True)
+        ctx.save_for_backward(logit, labels, lse, sums, *(() if cw is None else (cw,)))
+        ctx.ignore_index, ctx.smooth = ignore_index, smooth
+        ctx.mark_non_differentiable(correct)
+        return loss, correct
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_correct):
+        logit, labels, lse, sums, *cw = ctx.saved_tensors
+        g = grad_loss.to(dtype=torch.float32, device=logit.device).contiguous()          # stays on the device: no synchronisation
+        return _resize_dice_bwd(logit, labels, cw[0] if cw else None, lse, sums, g, ctx.ignore_index, ctx.smooth), None, None, None, None
+
+
+def resize_dice(logit, labels, ignore_index=255, smooth=1.0, class_weight=None):
+    """(loss, correct) of a head's low-resolution logits [B,C,h,w] (float32 / bfloat16) against labels [B,H,W] (uint8 / int64): mmseg's
+    DiceLoss(smooth, exponent=2, class_weight, loss_weight=1, ignore_index) of the logits resized bilinearly (align_corners=False) to
+    H x W — 1 / (C B) * the sum over images and classes i != ignore_index of class_weight_i (1 - (2 I + smooth) / (P2 + T + smooth)),
+    the sums of heads.dice_loss — as a 0-d float32 tensor differentiable w.r.t. `logit`, and the number of valid pixels whose argmax
+    equals the label as a 0-d int64 tensor (resize_cross_entropy's count).  Neither the resized logits, their softmax nor a one-hot
+    tensor is built and nothing is read back (ppn_resize_dice_fwd / ppn_resize_dice_bwd); a label outside [0, C) counts as ignored in
+    the numerator and, clamped, in the denominator.  class_weight: a float32 tensor [C] on the logits' device, or C floats, or None.
+    Without autograd recording the per-pixel buffer and the backward are skipped."""
+    if not (logit.is_cuda and labels.is_cuda):
+        raise RuntimeError("ppnet_amd.fused: GPU tensors only (no CPU fallback)")
+    if not resize_dice_ok(logit, labels):
+        raise ValueError(f"resize_dice: logits {tuple(logit.shape)} {logit.dtype} / labels {tuple(labels.shape)} {labels.dtype} "
+                         "are outside ppn_resize_dice_fwd's types and limits")
+    smooth = float(smooth)
+    if not 0.0 <= smooth < float("inf"):
+        raise ValueError(f"resize_dice: smooth {smooth} is negative or not finite")
+    cw = None
+    if class_weight is not None:
+        cw = torch.as_tensor(class_weight, dtype=torch.float32, device=logit.device).contiguous()
+        if cw.shape != (logit.shape[1],):
+            raise ValueError(f"resize_dice: class_weight {tuple(cw.shape)} for {logit.shape[1]} classes")
+    logit, labels = logit.contiguous(), labels.contiguous()
+    if torch.is_grad_enabled() and logit.requires_grad:
+        return _ResizeDiceFunction.apply(logit, labels, cw, int(ignore_index), smooth)
+    loss, correct, _, _ = _resize_dice_fwd(logit.detach(), labels, cw, int(ignore_index), smooth, False)
+    return loss, correct

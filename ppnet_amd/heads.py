@@ -95,14 +95,70 @@ def _loss_options(sampler, loss_decode, num_classes):
         sampler = OHEMPixelSampler(**cfg)
     elif sampler is not None and not isinstance(sampler, OHEMPixelSampler):
         raise NotImplementedError(f"pixel sampler {sampler!r}: a dict(type='OHEMPixelSampler', ...) or an OHEMPixelSampler")
-    cw = loss_decode.get("class_weight") if isinstance(loss_decode, dict) else None
-    if cw is not None:
-        if isinstance(cw, str):
-            raise NotImplementedError(f"class_weight {cw!r}: a list of {num_classes} floats (files are not read)")
-        cw = tuple(float(v) for v in cw)
-        if len(cw) != num_classes:
-            raise ValueError(f"class_weight has {len(cw)} entries for {num_classes} classes")
-    return sampler, cw
+    if isinstance(loss_decode, (list, tuple)):                               # a list: the first cross-entropy entry's
+        loss_decode = next((d for d in loss_decode if isinstance(d, dict) and d.get("type", _CE) == _CE), None)
+    elif isinstance(loss_decode, dict) and loss_decode.get("type", _CE) != _CE:
+        loss_decode = None                                                   # a single loss of another type: its weights are its own
+    return sampler, _class_weight_entry(loss_decode.get("class_weight") if isinstance(loss_decode, dict) else None, num_classes)
+
+
+_CE, _DICE = "CrossEntropyLoss", "DiceLoss"
+
+
+def _class_weight_entry(cw, num_classes):
+    """A loss's `class_weight` entry as a tuple of num_classes floats, or None; a file path (losses/utils.py:9-24) raises."""
+    if cw is None:
+        return None
+    if isinstance(cw, str):
+        raise NotImplementedError(f"class_weight {cw!r}: a list of {num_classes} floats (files are not read)")
+    cw = tuple(float(v) for v in cw)
+    if len(cw) != num_classes:
+        raise ValueError(f"class_weight has {len(cw)} entries for {num_classes} classes")
+    return cw
+
+
+def _single_ce(loss_decode):
+    """Whether loss_decode is the form every config had before loss lists: None, or ONE dict of type CrossEntropyLoss (or none)."""
+    return loss_decode is None or (isinstance(loss_decode, dict) and loss_decode.get("type", _CE) == _CE)
+
+
+def _loss_specs(loss_decode, num_classes):
+    """A head's `loss_decode` (decode_head.py:36-43,87-95: a dict or a sequence of dicts; None is the default CrossEntropyLoss) as a
+    tuple of specs, one dict per loss: `type` ('CrossEntropyLoss' | 'DiceLoss'), `loss_name` (default 'loss_ce' / 'loss_dice'; equal
+    names are summed, decode_head.py:246-262), `loss_weight`, `class_weight` (a tuple of num_classes floats or None) and, for DiceLoss
+    (losses/dice_loss.py:74-90), `smooth`, `exponent` and its own `ignore_index` (default 255).  Raised, never dropped silently
+    (NotImplementedError): another type (LovaszLoss needs a per-class device sort, FocalLoss the sigmoid form of an mmcv op),
+    class_weight as a file path, a reduction other than 'mean', and use_sigmoid=True (sigmoid / binary cross-entropy) inside a list or
+    on a DiceLoss.  A SINGLE CrossEntropyLoss dict is read as it always was: class_weight, and loss_weight by the auxiliary head
+    (FCNHead.loss_weight) — its other keys stay unread (resized_head_losses takes the head's weight for it, not the spec's)."""
+    if loss_decode is None:
+        entries = [{}]
+    elif isinstance(loss_decode, dict):
+        entries = [loss_decode]
+    elif isinstance(loss_decode, (list, tuple)) and len(loss_decode) > 0 and all(isinstance(d, dict) for d in loss_decode):
+        entries = list(loss_decode)
+    else:
+        raise TypeError(f"loss_decode must be a dict or a non-empty sequence of dicts, got {loss_decode!r}")
+    single = _single_ce(loss_decode)
+    specs = []
+    for d in entries:
+        typ = d.get("type", _CE)
+        if typ not in (_CE, _DICE):
+            raise NotImplementedError(f"loss type {typ!r}: CrossEntropyLoss and DiceLoss only (LovaszLoss, FocalLoss and the rest are not built)")
+        if not single:
+            if d.get("use_sigmoid", False):
+                raise NotImplementedError(f"{typ}(use_sigmoid=True): sigmoid / binary cross-entropy is not built")
+            if d.get("reduction", "mean") != "mean":
+                raise NotImplementedError(f"{typ}(reduction={d['reduction']!r}): 'mean' only")
+        spec = dict(type=typ, loss_name=str(d.get("loss_name", "loss_ce" if typ == _CE else "loss_dice")),
+                    loss_weight=float(d.get("loss_weight", 1.0)), class_weight=_class_weight_entry(d.get("class_weight"), num_classes))
+        if typ == _DICE:
+            ignore = d.get("ignore_index", 255)
+            spec.update(smooth=float(d.get("smooth", 1)), exponent=d.get("exponent", 2), ignore_index=-1 if ignore is None else int(ignore))
+            if not spec["smooth"] >= 0.0:
+                raise ValueError(f"DiceLoss(smooth={d.get('smooth')!r}): not negative")
+        specs.append(spec)
+    return tuple(specs)
 
 
 class SETRUPHead(nn.Module):
@@ -113,6 +169,7 @@ class SETRUPHead(nn.Module):
         assert kernel_size in (1, 3)
         self.in_index, self.align_corners = in_index, align_corners
         self.sampler, self.class_weight = _loss_options(sampler, loss_decode, num_classes)
+        self.loss_specs, self.loss_single_ce = _loss_specs(loss_decode, num_classes), _single_ce(loss_decode)
         self.norm = nn.LayerNorm(in_channels, eps=1e-6)
         self.up_convs = nn.ModuleList()
         cin = in_channels
@@ -191,6 +248,7 @@ class UPerHead(nn.Module):
         super().__init__()
         self.in_index, self.align_corners = tuple(in_index), align_corners
         self.sampler, self.class_weight = _loss_options(sampler, loss_decode, num_classes)
+        self.loss_specs, self.loss_single_ce = _loss_specs(loss_decode, num_classes), _single_ce(loss_decode)
         self.psp_modules = nn.ModuleList(
             nn.Sequential(nn.AdaptiveAvgPool2d(ps), _ConvModule(in_channels[-1], channels, 1)) for ps in pool_scales)
         self.bottleneck = _ConvModule(in_channels[-1] + len(pool_scales) * channels, channels, 3)
@@ -340,6 +398,7 @@ class UPerPUPHead(UPerHead):
         assert len(num_convs) == len(in_channels) == len(in_index)
         self.in_index, self.align_corners, self.num_convs = tuple(in_index), align_corners, tuple(num_convs)
         self.sampler, self.class_weight = _loss_options(sampler, loss_decode, num_classes)
+        self.loss_specs, self.loss_single_ce = _loss_specs(loss_decode, num_classes), _single_ce(loss_decode)
         # registration order = mmseg's state-dict order (BaseDecodeHead.__init__ makes conv_seg and dropout first, decode_head.py:102-106)
         self.conv_seg = nn.Conv2d(channels, num_classes, 1)
         self.dropout = nn.Dropout2d(dropout_ratio) if dropout_ratio > 0 else nn.Identity()
@@ -445,8 +504,10 @@ class FCNHead(nn.Module):
         super().__init__()
         assert num_convs >= 0 and dilation > 0
         self.in_index, self.align_corners, self.concat_input = in_index, align_corners, concat_input
-        self.loss_weight = float((loss_decode or {}).get("loss_weight", 1.0))
+        # the single cross-entropy form carries the head's weight here; every entry of another form carries its own (loss_specs)
+        self.loss_weight = float((loss_decode or {}).get("loss_weight", 1.0)) if _single_ce(loss_decode) else 1.0
         self.sampler, self.class_weight = _loss_options(sampler, loss_decode, num_classes)
+        self.loss_specs, self.loss_single_ce = _loss_specs(loss_decode, num_classes), _single_ce(loss_decode)
         if num_convs == 0:
             assert in_channels == channels
             self.convs = nn.Identity()
@@ -586,3 +647,70 @@ def resized_eval_areas(logit_lowres, gt, ignore_index=255, align_corners=False):
     with torch.no_grad():
         logit = F.interpolate(logit_lowres.float(), gt.shape[-2:], mode="bilinear", align_corners=align_corners)
         return eval_areas(logit.argmax(1), gt, logit.shape[1], ignore_index)
+
+
+def dice_loss(logit_fullres, gt, smooth=1.0, exponent=2, class_weight=None, loss_weight=1.0, ignore_index=255):
+    """mmseg's DiceLoss.forward (losses/dice_loss.py:12-47,92-123) for full-resolution logits [B,C,H,W] and labels [B,H,W], in torch
+    ops: any dtype, any exponent, CPU or GPU.  p = softmax(logit, 1), tc = the labels clamped into [0, C - 1], v = the label is valid;
+    per image and class  num = 2 sum_px p_i [tc == i] v + smooth,  den = sum_px (p_i^exponent + [tc == i]) + smooth  — the
+    denominator is NOT masked: an ignored label counts as the class its clamp lands on (255 as class C - 1), the reference's own quirk —
+    and  loss = loss_weight / C * sum_{i != ignore_index} class_weight_i * mean_b (1 - num / den)  (binary_dice_loss is itself
+    @weighted_loss: the batch mean; the class that equals ignore_index is skipped).  The head calls the reference's loss with
+    weight=seg_weight and ignore_index=255 as keyword arguments that fall into **kwards unused: a pixel sampler's weights do not reach
+    Dice, and the ignore_index is the loss's own.  v: a label equal to ignore_index OR outside [0, C) is not valid — this build's
+    rule; the reference masks by label != ignore_index only (the two agree on every in-range label and on ignore_index itself)."""
+    C = logit_fullres.shape[1]
+    gt = gt.long()
+    p = F.softmax(logit_fullres, dim=1).flatten(2)                                              # [B, C, HW]
+    onehot = F.one_hot(gt.clamp(0, C - 1), C).permute(0, 3, 1, 2).flatten(2).to(p.dtype)
+    valid = _valid_labels(gt, C, ignore_index).flatten(1).unsqueeze(1).to(p.dtype)
+    num = (p * onehot * valid).sum(2) * 2 + smooth
+    den = (p.pow(exponent) + onehot).sum(2) + smooth                                            # (0 / 1 to any positive power is itself)
+    per_class = (1 - num / den).mean(0)                                                         # [C]
+    if class_weight is not None:
+        per_class = per_class * _class_weight_tensor(class_weight, p.device, p.dtype)
+    keep = [i for i in range(C) if i != ignore_index]
+    return loss_weight * per_class[keep].sum() / C
+
+
+def resized_dice_losses(logit_lowres, gt, loss_weight=1.0, smooth=1.0, exponent=2, class_weight=None, ignore_index=255, align_corners=False):
+    """(loss_dice, acc_seg) of a head's LOW-resolution logits [B,C,h,w] resized bilinearly to the labels' size [B,H,W]: dice_loss and
+    decode_losses' accuracy.  CUDA float32 / bfloat16 logits with CUDA uint8 / int64 labels, align_corners False, exponent 2 and sizes
+    inside ppn_resize_dice_fwd's limits (C <= 256) run on the fused kernel pair (fused.resize_dice: neither the resized logits, their
+    softmax nor a one-hot tensor is built); PPNET_LIBRARY_LOSS=1 (read at call time), CPU tensors and everything else take the library
+    composition, F.interpolate of the float32 logits followed by dice_loss on int64 labels."""
+    if not align_corners and not os.environ.get("PPNET_LIBRARY_LOSS") and exponent == 2 and fused.resize_dice_ok(logit_lowres, gt):
+        cw = _class_weight_tensor(class_weight, logit_lowres.device, torch.float32)
+        dice, correct = fused.resize_dice(logit_lowres, gt, ignore_index, smooth, cw)
+        return loss_weight * dice, correct.float() * (100.0 / gt.numel())
+    logit = F.interpolate(logit_lowres.float(), gt.shape[-2:], mode="bilinear", align_corners=align_corners)
+    loss = dice_loss(logit, gt, smooth, exponent, class_weight, loss_weight, ignore_index)
+    with torch.no_grad():
+        acc = (logit.argmax(1) == gt).float().sum() * (100.0 / gt.numel())
+    return loss, acc
+
+
+def resized_head_losses(logit_lowres, gt, head, head_weight=1.0):
+    """BaseDecodeHead.losses (decode_head.py:231-265) for a head's low-resolution logits and its loss_specs: {loss_name: value, ...,
+    'acc_seg': value}.  CrossEntropyLoss entries go through resized_decode_losses — the head's pixel sampler and the entry's class
+    weights apply to them only — and DiceLoss entries through resized_dice_losses; entries with equal names add.  acc_seg is computed
+    once: by the cross-entropy kernel when there is such an entry, else from Dice's count.  The single cross-entropy form is the call
+    it always was: weight head_weight (1.0 for the decode head, FCNHead.loss_weight for the auxiliary one), ignore_index 255; every
+    entry of another form carries its own loss_weight, times head_weight."""
+    out, acc = {}, None
+    for spec in head.loss_specs:
+        w = head_weight if head.loss_single_ce else head_weight * spec["loss_weight"]
+        if spec["type"] == _CE:
+            loss, a = resized_decode_losses(logit_lowres, gt, w, align_corners=head.align_corners, class_weight=spec["class_weight"],
+                                            sampler=head.sampler)
+            if acc is None or acc[0] != _CE:
+                acc = (_CE, a)
+        else:
+            loss, a = resized_dice_losses(logit_lowres, gt, w, spec["smooth"], spec["exponent"], spec["class_weight"], spec["ignore_index"],
+                                          head.align_corners)
+            if acc is None:
+                acc = (_DICE, a)
+        name = spec["loss_name"]
+        out[name] = out[name] + loss if name in out else loss
+    out["acc_seg"] = acc[1]
+    return out

@@ -15,7 +15,8 @@ from .configs import (DINAT_BASE, NAT_BASE_UPER, NAT_BASE_UPERPUP, SWIN_BASE_SET
 from .dense import (IMG_MEAN, IMG_STD, LIBRARY_GEMM_BELOW_C, LIBRARY_GEMM_FROM_C, drop_path, normalize_images)  # noqa: F401
 from .dense import accumulate as _accumulate, bias32 as _bias32, library_width as _library_width, linear as _linear  # noqa: F401
 from .dense import mfma_weights as _mfma_weights, own_gemm_ok as _own_gemm_ok, use_mfma_conv as _use_mfma_conv  # noqa: F401
-from .heads import FCNHead, SETRUPHead, UPerHead, UPerPUPHead, _ConvModule, _Upsample, decode_losses, resized_decode_losses  # noqa: F401
+from .heads import (FCNHead, SETRUPHead, UPerHead, UPerPUPHead, _ConvModule, _Upsample, decode_losses, dice_loss,  # noqa: F401
+                    resized_decode_losses, resized_head_losses)
 from .heads import OHEMPixelSampler, eval_areas, ohem_weight, resized_eval_areas  # noqa: F401
 from .na import NeighborhoodAttention2D  # noqa: F401
 from .nat import NAT, ConvDownsampler, ConvTokenizer, DiNAT, Mlp, NATBlock, NATLayer, _fold_doc  # noqa: F401
@@ -79,8 +80,12 @@ class SegNet(nn.Module):
         (configs/_base_/models/dinat.py:3-46 merged with configs/dinat/dinat_base.py:5-24), or a whole config holding it under
         'model'.  A head's `sampler=dict(type='OHEMPixelSampler', thresh=..., min_kept=...)` and `loss_decode['class_weight']` (a list
         of floats) are read and applied by forward_train (heads._loss_options; another sampler type or a weight file raises);
-        `loss_decode['loss_weight']` is read by the auxiliary head.  mmcv-only keys (init_cfg, norm_cfg, conv_cfg, act_cfg,
-        in_patch_size, frozen_stages, the rest of loss_decode) are accepted and ignored where this build has one fixed choice."""
+        `loss_decode['loss_weight']` is read by the auxiliary head.  `loss_decode` may also be a DiceLoss dict or a list of
+        CrossEntropyLoss / DiceLoss dicts (heads._loss_specs): then every entry's type, loss_name, loss_weight and class_weight are
+        honoured, and DiceLoss's smooth, exponent and ignore_index; another loss type (LovaszLoss, FocalLoss, ...), use_sigmoid=True, a
+        reduction other than 'mean' and a weight file raise NotImplementedError.  A single CrossEntropyLoss dict is read as before: its
+        keys other than class_weight and loss_weight stay unread.  mmcv-only keys (init_cfg, norm_cfg, conv_cfg, act_cfg,
+        in_patch_size, frozen_stages) are accepted and ignored where this build has one fixed choice."""
         cfg = dict(cfg.get("model", cfg))
         typ = cfg.pop("type", "EncoderDecoder")
         if typ != "EncoderDecoder":
@@ -190,9 +195,11 @@ class SegNet(nn.Module):
         return out
 
     def forward_train(self, img, img_metas, gt_semantic_seg, **kwargs):
-        """encoder_decoder.py:122-152 with decode_head.py:209-237 (losses): {'decode.loss_ce', 'decode.acc_seg'} and, with an
+        """encoder_decoder.py:122-152 with decode_head.py:209-265 (losses): {'decode.loss_ce', 'decode.acc_seg'} and, with an
         auxiliary head, {'aux.loss_ce', 'aux.acc_seg'} (loss weights 1.0 / 0.4, ignore_index 255).  Each head's own pixel sampler and
-        class weights (decode_head.py:245-256) go with its logits."""
+        class weights (decode_head.py:245-256) go with its logits.  A head whose loss_decode is a list, or a DiceLoss, emits
+        '{prefix}.{loss_name}' for every name of its loss_specs (equal names summed) — '{prefix}.loss_dice' for DiceLoss — and one
+        '{prefix}.acc_seg'."""
         if self.prepared:
             raise RuntimeError("SegNet.prepare_inference() folded BatchNorm / LayerScale into the weights: build a fresh SegNet to train")
         feats = self.backbone(img)
@@ -203,9 +210,13 @@ class SegNet(nn.Module):
         heads = [("decode", self.decode_head, 1.0)] + [(f"aux_{i}" if isinstance(self.auxiliary_head, nn.ModuleList) else "aux", h, h.loss_weight)
                                                        for i, h in enumerate(self._aux_heads())]
         for name, head, w in heads:
-            # the head's output in its own dtype: the resize and the loss are one kernel pair on the GPU (heads.resized_decode_losses)
-            losses[f"{name}.loss_ce"], losses[f"{name}.acc_seg"] = resized_decode_losses(
-                head(feats), gt, w, align_corners=head.align_corners, class_weight=head.class_weight, sampler=head.sampler)
+            # the head's output in its own dtype: the resize and each loss are one kernel pair on the GPU (heads.resized_head_losses)
+            if head.loss_single_ce:                    # one CrossEntropyLoss, or none: the call it always was
+                losses[f"{name}.loss_ce"], losses[f"{name}.acc_seg"] = resized_decode_losses(
+                    head(feats), gt, w, align_corners=head.align_corners, class_weight=head.class_weight, sampler=head.sampler)
+                continue
+            for key, value in resized_head_losses(head(feats), gt, head, w).items():
+                losses[f"{name}.{key}"] = value
         return losses
 
     @torch.no_grad()

@@ -74,14 +74,19 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--augment", action="store_true",
                     help="train on the reference's train_pipeline (flip + photometric distortion, ppnet_amd.augment) instead of the bare palette image")
+    ap.add_argument("--dice-weight", type=float, default=None, metavar="W",
+                    help="train on loss_decode=[CrossEntropyLoss, DiceLoss(loss_weight=W)] (ppn_resize_dice_fwd / _bwd) instead of cross-entropy alone")
     args = ap.parse_args()
     from ppnet_amd import augment, edage, train
     from ppnet_amd.gennet import AEViT, load_trained
-    from ppnet_amd.segnet import SegNet
+    from ppnet_amd.segnet import DINAT_BASE, SegNet
     dev = torch.device("cuda:0")
     R = args.R
     torch.manual_seed(5)
-    net = SegNet().to(dev)                                            # DiNAT-B + SETR-UP, the configuration bench.py times
+    head = dict(DINAT_BASE["decode_head"])                            # DiNAT-B + SETR-UP, the configuration bench.py times
+    if args.dice_weight is not None:
+        head["loss_decode"] = [dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0), dict(type="DiceLoss", loss_weight=args.dice_weight)]
+    net = SegNet(decode_head=head).to(dev)
     trainer = train.segnet_trainer(net, dev)
     opt = train.segnet_optimizer(trainer, lr=args.lr)
     gen = AEViT(1, 1, R, 24).eval()
@@ -102,7 +107,7 @@ def main():
                 f.write(__doc__.split("\n\n")[0] + "\n\n" + "\n".join(lines) + "\n")
 
     emit({"config": "DiNAT-B + SETR-UP from scratch, float32", "R": R, "batch": batch, "lr": args.lr, "warmup_iters": args.warmup,
-          "schedule_horizon": args.max_iters, "augment": bool(args.augment), "parameters": sum(p.numel() for p in net.parameters()), "minutes": args.minutes})
+          "schedule_horizon": args.max_iters, "augment": bool(args.augment), "dice_weight": args.dice_weight, "parameters": sum(p.numel() for p in net.parameters()), "minutes": args.minutes})
     r0 = evaluate(torch, net, dev, R, gen)
     emit({"step": 0, **{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r0.items()}})
     t0 = time.time()
