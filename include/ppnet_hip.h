@@ -70,7 +70,8 @@ extern "C" {
  * 111 = ppn_na2d_bwd_vpad, ppn_na2d_bwd_vpad_workspace.  ppn_resize_ce_workspace, ppn_resize_ce_fwd and ppn_resize_ce_bwd joined at
  * 111 too, and so did ppn_seg_eval and ppn_augment_params / ppn_augment_codes / ppn_augment_rgb: new symbols change no existing
  * argument list and remove nothing, which is all the version guards against.  ppn_ohem_ce_workspace, ppn_ohem_ce_fwd and
- * ppn_ohem_ce_bwd joined at 111 in the same way, and so did ppn_resize_dice_workspace, ppn_resize_dice_fwd and ppn_resize_dice_bwd. */
+ * ppn_ohem_ce_bwd joined at 111 in the same way, and so did ppn_resize_dice_workspace, ppn_resize_dice_fwd and ppn_resize_dice_bwd, and
+ * ppn_upsample2x_nhwc_bwd, ppn_upsample2x_concat_nhwc_bwd and ppn_resize_concat_nhwc_bwd. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -557,6 +558,30 @@ int ppn_resize_concat4_nhwc(const void* x0, const void* x1, const void* x2, cons
  * `torch.cat([x] + [resize(ppm(x), size=x.shape[2:], mode='bilinear')...], dim=1)` with the pooled maps smaller than x. */
 int ppn_resize_concat_nhwc(const void* const* x, const int32_t* hw, const int32_t* channels, int32_t n, void* out, int32_t B, int32_t dtype,
                            void* stream);
+/* The backward of the three up-sampling entries above, for training the decode heads on them.  All are gathers: one writer per dx
+ * element, no atomics, float32 sums in a fixed order, one rounding to the tensor type — two calls on the same inputs give the same
+ * bits — and every dx element is written (no zero-filled buffer is assumed).  NHWC, channels % 8 == 0, dtype 0 = float32,
+ * 1 = bfloat16, 64-bit offsets.  Every argument check returns PPN_E_INVALID before any HIP call.
+ *
+ * ppn_upsample2x_nhwc_bwd: dy [B][2H][2W][C] -> dx [B][H][W][C], the exact transpose of ppn_upsample2x_nhwc: input row r gathers
+ * output rows 2r-1, 2r, 2r+1, 2r+2 with weights 0.25 [r >= 1], w0, w1, 0.25 [r <= H-2], w0 = 1 if r == 0 else 0.75, w1 = 1 if
+ * r == H-1 else 0.75 (the clamped borders fold onto the edge rows), the same along x: 16 taps per element.  x, when not NULL, is the
+ * forward's input BEFORE its folded ReLU ([B][H][W][C]): dx is zeroed where x <= 0.  Also the backward of ppn_upsample2x_add_nhwc with
+ * respect to its coarse operand (x = NULL; with respect to `add` it is the identity).  H == 1 and W == 1 are valid.  Limits, as the
+ * forward's: B (H + 1) < 2^31, (W + 1) C / 8 <= 65535 * 256, H and W < 2^30. */
+int ppn_upsample2x_nhwc_bwd(const void* dy, const void* x, void* dx, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
+/* The backward of ppn_upsample2x_concat_nhwc: dx[l] [B][H][W][channels[l]] = the transpose above applied to channels
+ * [off_l, off_l + channels[l]) of dout [B][2H][2W][sum channels] (HOST arrays of n = 1..8 pointers / channel counts), one launch.
+ * The forward entry's limits. */
+int ppn_upsample2x_concat_nhwc_bwd(const void* dout, void* const* dx, const int32_t* channels, int32_t n, int32_t B, int32_t H, int32_t W,
+                                   int32_t dtype, void* stream);
+/* The backward of ppn_resize_concat_nhwc: dx[l] [B][hw[2 l]][hw[2 l + 1]][channels[l]] from dout [B][hw[0]][hw[1]][sum channels].  A
+ * level of level 0's size receives a copy of its channel slice; otherwise input pixel (r, q) gathers every output pixel whose taps
+ * (y0, y1) x (x0, x1) include it, with the weights the forward kernel's own float32 formula gives that output, so forward and
+ * backward agree on every tap.  No level may be larger than level 0 (PPN_E_INVALID); B hw[0] hw[1] < 2^31 and fewer than 2^31
+ * blocks of 256 threads (B hw[0] hw[1] max(channels) / 8 work-items at most). */
+int ppn_resize_concat_nhwc_bwd(const void* dout, void* const* dx, const int32_t* hw, const int32_t* channels, int32_t n, int32_t B, int32_t dtype,
+                               void* stream);
 /* The pyramid pooling module's pools (psp_head.py:33-38: `nn.AdaptiveAvgPool2d(s)` for each pool scale) of one NHWC tensor
  * x [B][H][W][C] in one launch: y[k] [B][scales[k]][scales[k]][C], k < n <= 4 (HOST arrays), PyTorch's bins
  * (rows floor(i H / s) .. ceil((i + 1) H / s) - 1), summed in float32.  C % 8 == 0. */

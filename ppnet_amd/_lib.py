@@ -59,7 +59,8 @@ EXPORTS = ("ppn_version", "ppn_error_string", "ppn_last_hip_error", "ppn_polyfit
            "ppn_resize_ce_workspace", "ppn_resize_ce_fwd", "ppn_resize_ce_bwd", "ppn_seg_eval",
            "ppn_augment_params", "ppn_augment_codes", "ppn_augment_rgb",
            "ppn_ohem_ce_workspace", "ppn_ohem_ce_fwd", "ppn_ohem_ce_bwd",
-           "ppn_resize_dice_workspace", "ppn_resize_dice_fwd", "ppn_resize_dice_bwd")
+           "ppn_resize_dice_workspace", "ppn_resize_dice_fwd", "ppn_resize_dice_bwd",
+           "ppn_upsample2x_nhwc_bwd", "ppn_upsample2x_concat_nhwc_bwd", "ppn_resize_concat_nhwc_bwd")
 
 
 def _load():
@@ -134,6 +135,9 @@ def _load():
     lib.ppn_upsample2x_nhwc.argtypes = [_p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
     lib.ppn_upsample2x_nhwc_bias.argtypes = [_p, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
     lib.ppn_upsample2x_concat_nhwc.argtypes = [C.POINTER(_p), C.POINTER(C.c_int32), C.c_int32, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
+    lib.ppn_upsample2x_nhwc_bwd.argtypes = [_p, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
+    lib.ppn_upsample2x_concat_nhwc_bwd.argtypes = [_p, C.POINTER(_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
+    lib.ppn_resize_concat_nhwc_bwd.argtypes = [_p, C.POINTER(_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, _p]
     lib.ppn_grid_to_image.argtypes = [_p, _p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, _p]
     lib.ppn_seg_labels_2class.argtypes = [_p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
     lib.ppn_bias_act_nhwc.argtypes = [_p, _p, C.c_int64, C.c_int32, C.c_float, C.c_int32, _p]

@@ -724,6 +724,59 @@ int ppn_resize_concat_nhwc(const void* const* x, const int32_t* hw, const int32_
     return PPN_OK;
 }
 
+// The launch limits of the x2 kernels, forward and backward (the backward's grid is the smaller one: it walks 2 x 2 input blocks):
+// B (H + 1) block rows < 2^31, at most 65535 pieces of 256 threads per block row; 2H, 2W stay 32-bit.
+static bool up2x_grid_ok(int32_t B, int32_t H, int32_t W, long long cmax) {
+    return H < (1 << 30) && W < (1 << 30) && (long long)B * (H + 1) < (1LL << 31) && (((long long)W + 1) * (cmax / 8) + 255) / 256 <= 65535;
+}
+
+int ppn_upsample2x_nhwc_bwd(const void* dy, const void* x, void* dx, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream) {
+    if (!dy || !dx || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) != 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;
+    if (!up2x_grid_ok(B, H, W, C)) return PPN_E_INVALID;
+    const int e = ppn::upsample2x_bwd_launch(dy, x, dx, B, H, W, C, dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_upsample2x_concat_nhwc_bwd(const void* dout, void* const* dx, const int32_t* channels, int32_t n, int32_t B, int32_t H, int32_t W,
+                                   int32_t dtype, void* stream) {
+    if (!dout || !dx || !channels || n <= 0 || n > 8 || B <= 0 || H <= 0 || W <= 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;
+    int ch[8];
+    long long total = 0, cmax = 0;
+    for (int l = 0; l < n; ++l) {
+        if (!dx[l] || channels[l] <= 0 || (channels[l] % 8) != 0) return PPN_E_INVALID;
+        ch[l] = channels[l];
+        total += channels[l];
+        cmax = channels[l] > cmax ? channels[l] : cmax;
+    }
+    if (total > 0x7fffffffLL || !up2x_grid_ok(B, H, W, cmax)) return PPN_E_INVALID;
+    const int e = ppn::upsample2x_concat_bwd_launch(dout, dx, ch, n, B, H, W, dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_resize_concat_nhwc_bwd(const void* dout, void* const* dx, const int32_t* hw, const int32_t* channels, int32_t n, int32_t B, int32_t dtype,
+                               void* stream) {
+    if (!dout || !dx || !hw || !channels || n <= 0 || n > 8 || B <= 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;
+    int h[16], ch[8];
+    long long total = 0, cmax = 0;
+    for (int l = 0; l < n; ++l) {
+        if (!dx[l] || hw[2 * l] <= 0 || hw[2 * l + 1] <= 0 || channels[l] <= 0 || (channels[l] % 8) != 0) return PPN_E_INVALID;
+        if (hw[2 * l] > hw[0] || hw[2 * l + 1] > hw[1]) return PPN_E_INVALID;          // no level larger than level 0
+        h[2 * l] = hw[2 * l]; h[2 * l + 1] = hw[2 * l + 1]; ch[l] = channels[l];
+        total += channels[l];
+        cmax = channels[l] > cmax ? channels[l] : cmax;
+    }
+    // launch geometry (resize_concat_bwd_launch): one thread per 8 channels of an input pixel, fewer than 2^31 blocks of 256 per level
+    // (levels are no larger than level 0, so its pixel count bounds them all); the channel offsets stay 32-bit
+    if (total > 0x7fffffffLL || (long long)hw[0] * hw[1] >= (1LL << 31) || (long long)B * hw[0] * hw[1] >= (1LL << 31) ||
+        ((long long)B * hw[0] * hw[1] * (cmax / 8) + 255) / 256 >= (1LL << 31))
+        return PPN_E_INVALID;
+    const int e = ppn::resize_concat_bwd_launch(dout, dx, h, ch, n, B, dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_adaptive_pools_nhwc(const void* x, void* const* y, const int32_t* scales, int32_t n, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
                             void* stream) {
     if (!x || !y || !scales || n <= 0 || n > 4 || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) != 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;

@@ -128,6 +128,10 @@ int resize_concat_launch(const void* const* x, const int* hw, const int* ch, int
 int adaptive_pools_launch(const void* x, void* const* y, const int* scales, int n, int B, int H, int W, int C, int dtype, hipStream_t stream);
 int upsample2x_launch(const void* x, const void* bias, const void* add, void* y, int B, int H, int W, int C, int relu, int dtype, hipStream_t stream);
 int upsample2x_concat_launch(const void* const* x, const int* ch, int n, void* y, int B, int H, int W, int dtype, hipStream_t stream);
+// upsample_bwd.hip: the transposes of the three launches above (x may be null: no folded ReLU)
+int upsample2x_bwd_launch(const void* dy, const void* x, void* dx, int B, int H, int W, int C, int dtype, hipStream_t stream);
+int upsample2x_concat_bwd_launch(const void* dout, void* const* dx, const int* ch, int n, int B, int H, int W, int dtype, hipStream_t stream);
+int resize_concat_bwd_launch(const void* dout, void* const* dx, const int* hw, const int* ch, int n, int B, int dtype, hipStream_t stream);
 int conv3x3_c1_launch(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int Cout, float slope, int dtype,
                       hipStream_t stream);
 int conv3x3_to1_launch(const void* x, const float* w, float bias, void* y, int B, int H, int W, int Cin, int dtype, hipStream_t stream);

@@ -3,12 +3,15 @@
 Inference runs the HIP kernels below.  When autograd is recording (a training step, ppnet_amd/train.py) the same functions
 compose differentiable torch ops instead — the fused kernels are forward-only; the hand-written backwards are the
 attentions': neighbourhood (ppn_na2d_bwd, na.na2d_autograd), ViT's global one (ppn_mhsa_bwd, vit.mhsa_autograd) and Swin's window one
-(ppn_swin_wmsa_bwd, swin.wmsa_autograd) — and the heads' loss: bilinear resize + cross-entropy (ppn_resize_ce_bwd,
-resize_cross_entropy below)."""
+(ppn_swin_wmsa_bwd, swin.wmsa_autograd) — the heads' loss: bilinear resize + cross-entropy (ppn_resize_ce_bwd,
+resize_cross_entropy below) — and the heads' bilinear up-sampling (ppn_upsample2x_nhwc_bwd, ppn_upsample2x_concat_nhwc_bwd,
+ppn_resize_concat_nhwc_bwd: upsample2x_nhwc, upsample2x_add, upsample2x_concat and resize_concat record their own kernels)."""
 import ctypes
+import os
 
 import torch
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 
@@ -162,26 +165,96 @@ def residual_layer_norm(x, a, gamma, ln_next, pad_to=None):
     return x, y
 
 
-def upsample2x_nhwc(x_nchw_cl, relu=False, bias=None):
-    """Bilinear x2 (align_corners=False) of a channels_last [B,C,H,W] tensor, optionally with a per-channel bias and a
-    ReLU folded into the loads (conv -> folded BN -> ReLU -> Upsample with a bias-free library convolution).  Returns a
-    channels_last [B,C,2H,2W] tensor (zero-copy views on both sides)."""
-    if recording(x_nchw_cl, bias):
-        t = x_nchw_cl if bias is None else x_nchw_cl + bias.view(1, -1, 1, 1)
-        return F.interpolate(F.relu(t) if relu else t, scale_factor=2.0, mode="bilinear", align_corners=False)
-    if not x_nchw_cl.is_cuda:
-        raise RuntimeError("ppnet_amd.fused: GPU tensors only (no CPU fallback)")
-    x = x_nchw_cl.permute(0, 2, 3, 1)
-    if not x.is_contiguous():
-        x = x.contiguous()
+def library_upsample():
+    """PPNET_LIBRARY_UPSAMPLE=1 (read at call time, like PPNET_LIBRARY_LOSS): while autograd records, the decode heads' up-sampling
+    takes the library composition (F.relu, F.interpolate, +, torch.cat and the library's scatter backward) instead of the HIP
+    kernels and their backward entries.  Inference is untouched."""
+    return bool(os.environ.get("PPNET_LIBRARY_UPSAMPLE"))
+
+
+def _upsample_kernels_record(*tensors):
+    """Whether the up-sampling Functions below take these [B,C,H,W] tensors while autograd records: CUDA, float32 / bfloat16 of one
+    dtype, channels a multiple of 8, and the knob off.  Everything else keeps the library composition."""
+    t0 = tensors[0]
+    return (not library_upsample() and all(t.is_cuda and t.dim() == 4 and t.dtype == t0.dtype and t.device == t0.device and t.shape[1] % 8 == 0
+                                           and t.numel() > 0 for t in tensors) and t0.dtype in _DT)
+
+
+# Output elements from which the SINGLE-operator forms (upsample2x_nhwc, upsample2x_add) record their kernels.  Below, the library
+# composition is two framework ops each way, whose dispatch costs less host time than one Python autograd node and two ctypes
+# launches, and the tensors are too small for the kernels' bandwidth to pay that back (tools/upsample_bwd_timing.py, DESIGN.md
+# section 21: float32 slower up to 4.2 M output elements and faster from 12.8 M; bfloat16 — where the library's atomics round after
+# every add — slower at 1.05 M and faster from 1.6 M).  upsample2x_concat and resize_concat replace 4 to 10 framework ops each way
+# and were level or faster on every shape: no gate.
+UPSAMPLE_RECORD_MIN = {torch.float32: 1 << 23, torch.bfloat16: (1 << 20) + 1}
+
+
+def _nhwc(t):
+    """The contiguous [B,H,W,C] view of a [B,C,H,W] tensor (a copy only when it is not channels_last)."""
+    x = t.permute(0, 2, 3, 1)
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def _stream(t):
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _upsample2x_fwd(x, bias, relu):
+    """ppn_upsample2x_nhwc_bias on a contiguous [B,H,W,C] tensor -> [B,2H,2W,C]."""
     B, H, W, C = x.shape
     y = torch.empty(B, 2 * H, 2 * W, C, dtype=x.dtype, device=x.device)
     with torch.cuda.device(x.device):
         bias = bias.detach().to(x.dtype).contiguous() if bias is not None else None
-        rc = L.lib.ppn_upsample2x_nhwc_bias(_p(x), _p(bias), _p(y), B, H, W, C, 1 if relu else 0, _DT[x.dtype],
-                                            ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+        rc = L.lib.ppn_upsample2x_nhwc_bias(_p(x), _p(bias), _p(y), B, H, W, C, 1 if relu else 0, _DT[x.dtype], _stream(x))
     L.check(rc, "ppn_upsample2x_nhwc_bias")
-    return y.permute(0, 3, 1, 2)
+    return y
+
+
+def _upsample2x_bwd(dy, x):
+    """ppn_upsample2x_nhwc_bwd: contiguous dy [B,2H,2W,C] -> dx [B,H,W,C]; x (or None) the forward's input before its folded ReLU."""
+    B, H2, W2, C = dy.shape
+    H, W = H2 // 2, W2 // 2
+    assert x is None or (tuple(x.shape) == (B, H, W, C) and x.dtype == dy.dtype and x.is_contiguous())
+    dx = torch.empty(B, H, W, C, dtype=dy.dtype, device=dy.device)
+    with torch.cuda.device(dy.device):
+        rc = L.lib.ppn_upsample2x_nhwc_bwd(_p(dy), _p(x), _p(dx), B, H, W, C, _DT[dy.dtype], _stream(dy))
+    L.check(rc, "ppn_upsample2x_nhwc_bwd")
+    return dx
+
+
+class _Upsample2xFunction(torch.autograd.Function):
+    """ppn_upsample2x_nhwc / ppn_upsample2x_nhwc_bwd.  Saves the input only when the ReLU is folded in (its sign is the mask)."""
+
+    @staticmethod
+    def forward(ctx, x_nchw, relu):
+        x = _nhwc(x_nchw)
+        ctx.relu = bool(relu)
+        if ctx.relu:
+            ctx.save_for_backward(x)
+        return _upsample2x_fwd(x, None, ctx.relu).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        x = ctx.saved_tensors[0] if ctx.relu else None
+        return _upsample2x_bwd(_nhwc(grad), x).permute(0, 3, 1, 2), None
+
+
+def upsample2x_nhwc(x_nchw_cl, relu=False, bias=None):
+    """Bilinear x2 (align_corners=False) of a channels_last [B,C,H,W] tensor, optionally with a per-channel bias and a
+    ReLU folded into the loads (conv -> folded BN -> ReLU -> Upsample with a bias-free library convolution).  Returns a
+    channels_last [B,C,2H,2W] tensor (zero-copy views on both sides).  While autograd records, the same kernel runs behind
+    _Upsample2xFunction (backward: ppn_upsample2x_nhwc_bwd); a bias (prepared modules only, which do not train), a channel count
+    that is no multiple of 8, an output below UPSAMPLE_RECORD_MIN elements and PPNET_LIBRARY_UPSAMPLE=1 take the library
+    composition then."""
+    if recording(x_nchw_cl, bias):
+        if bias is None and _upsample_kernels_record(x_nchw_cl) and 4 * x_nchw_cl.numel() >= UPSAMPLE_RECORD_MIN[x_nchw_cl.dtype]:
+            return _Upsample2xFunction.apply(x_nchw_cl, relu)
+        t = x_nchw_cl if bias is None else x_nchw_cl + bias.view(1, -1, 1, 1)
+        return F.interpolate(F.relu(t) if relu else t, scale_factor=2.0, mode="bilinear", align_corners=False)
+    if not x_nchw_cl.is_cuda:
+        raise RuntimeError("ppnet_amd.fused: GPU tensors only (no CPU fallback)")
+    return _upsample2x_fwd(_nhwc(x_nchw_cl), bias, relu).permute(0, 3, 1, 2)
 
 
 def upsample2x_add_(fine, coarse):
@@ -198,50 +271,153 @@ def upsample2x_add_(fine, coarse):
     return fine
 
 
-def upsample2x_concat(levels):
-    """Up to eight channels_last [B,C_l,H,W] tensors of ONE size, each bilinearly up-sampled x2 (align_corners=False) into its channel
-    range of one output, in ONE kernel (ppn_upsample2x_concat_nhwc): UPerPUPHead's last Upsample of every FPN chain and the
-    concatenation behind them (uper_pup_head.py:121-128).  Returns a channels_last [B, sum C_l, 2H, 2W] tensor."""
-    assert 1 <= len(levels) <= 8
-    xs = []
-    for t in levels:
-        x = t.permute(0, 2, 3, 1)
-        xs.append(x if x.is_contiguous() else x.contiguous())
+def _upsample2x_add_fwd(f, c):
+    """ppn_upsample2x_add_nhwc out of place on contiguous NHWC tensors: a new [B,2H,2W,C] tensor = f + (c resized x2)."""
+    B, H, W, C = c.shape
+    if tuple(f.shape) != (B, 2 * H, 2 * W, C):
+        raise RuntimeError(f"upsample2x_add: fine {tuple(f.shape)} is not twice coarse {tuple(c.shape)} (NHWC)")
+    y = torch.empty_like(f)
+    with torch.cuda.device(f.device):
+        rc = L.lib.ppn_upsample2x_add_nhwc(_p(c), _p(f), _p(y), B, H, W, C, _DT[f.dtype], _stream(f))
+    L.check(rc, "ppn_upsample2x_add_nhwc")
+    return y
+
+
+class _Upsample2xAddFunction(torch.autograd.Function):
+    """ppn_upsample2x_add_nhwc out of place.  Saves nothing: the gradient passes through to `fine` and goes through
+    ppn_upsample2x_nhwc_bwd to `coarse`."""
+
+    @staticmethod
+    def forward(ctx, fine, coarse):
+        return _upsample2x_add_fwd(_nhwc(fine), _nhwc(coarse)).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        d_coarse = _upsample2x_bwd(_nhwc(grad), None).permute(0, 3, 1, 2) if ctx.needs_input_grad[1] else None
+        return (grad if ctx.needs_input_grad[0] else None), d_coarse
+
+
+def upsample2x_add(fine, coarse):
+    """fine + bilinear x2 (align_corners=False) of coarse as a NEW channels_last tensor: the differentiable form of upsample2x_add_
+    (one ppn_upsample2x_add_nhwc; backward: the identity to `fine`, ppn_upsample2x_nhwc_bwd to `coarse`).  CPU tensors, other dtypes,
+    channels that are no multiple of 8 and, while autograd records, an output below UPSAMPLE_RECORD_MIN elements and
+    PPNET_LIBRARY_UPSAMPLE=1 take interpolate + add."""
+    kernel_types = fine.is_cuda and coarse.is_cuda and fine.dtype == coarse.dtype and fine.dtype in _DT and coarse.shape[1] % 8 == 0
+    if recording(fine, coarse):
+        if _upsample_kernels_record(fine, coarse) and fine.numel() >= UPSAMPLE_RECORD_MIN[fine.dtype]:
+            return _Upsample2xAddFunction.apply(fine, coarse)
+    elif kernel_types:
+        return _upsample2x_add_fwd(_nhwc(fine), _nhwc(coarse)).permute(0, 3, 1, 2)
+    return fine + F.interpolate(coarse, scale_factor=2.0, mode="bilinear", align_corners=False)
+
+
+def _upsample2x_concat_fwd(xs):
     B, H, W, _ = xs[0].shape
-    if any(tuple(x.shape[:3]) != (B, H, W) for x in xs):
-        raise RuntimeError(f"upsample2x_concat: levels of different sizes {[tuple(x.shape[1:3]) for x in xs]}")
-    assert all(x.is_cuda and x.dtype == xs[0].dtype and x.shape[3] % 8 == 0 for x in xs) and xs[0].dtype in _DT
     n = len(xs)
     out = torch.empty(B, 2 * H, 2 * W, sum(x.shape[3] for x in xs), dtype=xs[0].dtype, device=xs[0].device)
     ptrs = (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
     ch = (ctypes.c_int32 * n)(*[x.shape[3] for x in xs])
     with torch.cuda.device(out.device):
-        rc = L.lib.ppn_upsample2x_concat_nhwc(ptrs, ch, n, _p(out), B, H, W, _DT[xs[0].dtype],
-                                              ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream))
+        rc = L.lib.ppn_upsample2x_concat_nhwc(ptrs, ch, n, _p(out), B, H, W, _DT[xs[0].dtype], _stream(out))
     L.check(rc, "ppn_upsample2x_concat_nhwc")
-    return out.permute(0, 3, 1, 2)
+    return out
 
 
-def resize_concat(levels):
-    """Up to eight channels_last [B,C_l,H_l,W_l] tensors, each bilinearly resized (align_corners=False) to the FIRST one's size and
-    concatenated over channels in ONE kernel (ppn_resize_concat_nhwc): UPerHead's FPN output assembly (uper_head.py:117-127) and
-    its pyramid pooling module's output (psp_head.py:48-60).  Returns a channels_last [B, sum C_l, H_0, W_0] tensor."""
+class _Upsample2xConcatFunction(torch.autograd.Function):
+    """ppn_upsample2x_concat_nhwc / ppn_upsample2x_concat_nhwc_bwd.  Saves nothing but the channel counts."""
+
+    @staticmethod
+    def forward(ctx, *levels):
+        xs = [_nhwc(t) for t in levels]
+        ctx.channels = [x.shape[3] for x in xs]
+        return _upsample2x_concat_fwd(xs).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        dout = _nhwc(grad)
+        B, H2, W2, _ = dout.shape
+        n = len(ctx.channels)
+        dxs = [torch.empty(B, H2 // 2, W2 // 2, c, dtype=dout.dtype, device=dout.device) for c in ctx.channels]
+        ptrs = (ctypes.c_void_p * n)(*[d.data_ptr() for d in dxs])
+        ch = (ctypes.c_int32 * n)(*ctx.channels)
+        with torch.cuda.device(dout.device):
+            rc = L.lib.ppn_upsample2x_concat_nhwc_bwd(_p(dout), ptrs, ch, n, B, H2 // 2, W2 // 2, _DT[dout.dtype], _stream(dout))
+        L.check(rc, "ppn_upsample2x_concat_nhwc_bwd")
+        return tuple(d.permute(0, 3, 1, 2) for d in dxs)
+
+
+def upsample2x_concat(levels):
+    """Up to eight channels_last [B,C_l,H,W] tensors of ONE size, each bilinearly up-sampled x2 (align_corners=False) into its channel
+    range of one output, in ONE kernel (ppn_upsample2x_concat_nhwc): UPerPUPHead's last Upsample of every FPN chain and the
+    concatenation behind them (uper_pup_head.py:121-128).  Returns a channels_last [B, sum C_l, 2H, 2W] tensor.  Differentiable
+    (ppn_upsample2x_concat_nhwc_bwd); PPNET_LIBRARY_UPSAMPLE=1 composes interpolate + torch.cat while autograd records."""
     assert 1 <= len(levels) <= 8
-    xs = []
-    for t in levels:
-        x = t.permute(0, 2, 3, 1)
-        xs.append(x if x.is_contiguous() else x.contiguous())
+    if any(tuple(t.shape[2:]) != tuple(levels[0].shape[2:]) or t.shape[0] != levels[0].shape[0] for t in levels):
+        raise RuntimeError(f"upsample2x_concat: levels of different sizes {[tuple(t.shape[2:]) for t in levels]}")
+    if recording(*levels):
+        if _upsample_kernels_record(*levels):
+            return _Upsample2xConcatFunction.apply(*levels)
+        return torch.cat([F.interpolate(t, scale_factor=2.0, mode="bilinear", align_corners=False) for t in levels], dim=1)
+    xs = [_nhwc(t) for t in levels]
+    assert all(x.is_cuda and x.dtype == xs[0].dtype and x.shape[3] % 8 == 0 for x in xs) and xs[0].dtype in _DT
+    return _upsample2x_concat_fwd(xs).permute(0, 3, 1, 2)
+
+
+def _resize_concat_fwd(xs):
     B, H0, W0, _ = xs[0].shape
-    assert all(x.is_cuda and x.dtype == xs[0].dtype and x.shape[0] == B and x.shape[3] % 8 == 0 for x in xs) and xs[0].dtype in _DT
     n = len(xs)
     out = torch.empty(B, H0, W0, sum(x.shape[3] for x in xs), dtype=xs[0].dtype, device=xs[0].device)
     ptrs = (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
     hw = (ctypes.c_int32 * (2 * n))(*[v for x in xs for v in (x.shape[1], x.shape[2])])
     ch = (ctypes.c_int32 * n)(*[x.shape[3] for x in xs])
     with torch.cuda.device(out.device):
-        rc = L.lib.ppn_resize_concat_nhwc(ptrs, hw, ch, n, _p(out), B, _DT[xs[0].dtype], ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream))
+        rc = L.lib.ppn_resize_concat_nhwc(ptrs, hw, ch, n, _p(out), B, _DT[xs[0].dtype], _stream(out))
     L.check(rc, "ppn_resize_concat_nhwc")
-    return out.permute(0, 3, 1, 2)
+    return out
+
+
+class _ResizeConcatFunction(torch.autograd.Function):
+    """ppn_resize_concat_nhwc / ppn_resize_concat_nhwc_bwd.  Saves nothing but the levels' sizes and channel counts."""
+
+    @staticmethod
+    def forward(ctx, *levels):
+        xs = [_nhwc(t) for t in levels]
+        ctx.sizes = [tuple(x.shape[1:]) for x in xs]
+        return _resize_concat_fwd(xs).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        dout = _nhwc(grad)
+        B, n = dout.shape[0], len(ctx.sizes)
+        dxs = [torch.empty(B, h, w, c, dtype=dout.dtype, device=dout.device) for h, w, c in ctx.sizes]
+        ptrs = (ctypes.c_void_p * n)(*[d.data_ptr() for d in dxs])
+        hw = (ctypes.c_int32 * (2 * n))(*[v for h, w, _ in ctx.sizes for v in (h, w)])
+        ch = (ctypes.c_int32 * n)(*[c for _, _, c in ctx.sizes])
+        with torch.cuda.device(dout.device):
+            rc = L.lib.ppn_resize_concat_nhwc_bwd(_p(dout), ptrs, hw, ch, n, B, _DT[dout.dtype], _stream(dout))
+        L.check(rc, "ppn_resize_concat_nhwc_bwd")
+        return tuple(d.permute(0, 3, 1, 2) for d in dxs)
+
+
+def resize_concat(levels):
+    """Up to eight channels_last [B,C_l,H_l,W_l] tensors, each bilinearly resized (align_corners=False) to the FIRST one's size and
+    concatenated over channels in ONE kernel (ppn_resize_concat_nhwc): UPerHead's FPN output assembly (uper_head.py:117-127) and
+    its pyramid pooling module's output (psp_head.py:48-60).  Returns a channels_last [B, sum C_l, H_0, W_0] tensor.  Differentiable
+    (ppn_resize_concat_nhwc_bwd) when no level is larger than the first; otherwise, and with PPNET_LIBRARY_UPSAMPLE=1, interpolate +
+    torch.cat are composed while autograd records."""
+    assert 1 <= len(levels) <= 8
+    if recording(*levels):
+        H0, W0 = levels[0].shape[2:]
+        if _upsample_kernels_record(*levels) and all(t.shape[0] == levels[0].shape[0] and t.shape[2] <= H0 and t.shape[3] <= W0 for t in levels):
+            return _ResizeConcatFunction.apply(*levels)
+        return torch.cat([levels[0]] + [F.interpolate(t, size=(H0, W0), mode="bilinear", align_corners=False) for t in levels[1:]], dim=1)
+    xs = [_nhwc(t) for t in levels]
+    B = xs[0].shape[0]
+    assert all(x.is_cuda and x.dtype == xs[0].dtype and x.shape[0] == B and x.shape[3] % 8 == 0 for x in xs) and xs[0].dtype in _DT
+    return _resize_concat_fwd(xs).permute(0, 3, 1, 2)
 
 
 def resize_concat4(levels):

@@ -259,8 +259,8 @@ class UPerHead(nn.Module):
 
     def _resize(self, x, size):
         if (x.is_cuda and not self.align_corners and tuple(size) == (2 * x.shape[2], 2 * x.shape[3]) and x.shape[1] % 8 == 0
-                and x.dtype in (torch.float32, torch.bfloat16) and not fused.recording(x)):
-            return fused.upsample2x_nhwc(x)                                  # the FPN's x2 steps: the build's NHWC kernel
+                and x.dtype in (torch.float32, torch.bfloat16) and not (fused.library_upsample() and fused.recording(x))):
+            return fused.upsample2x_nhwc(x)                                  # the FPN's x2 steps: the build's NHWC kernel (it records its own backward)
         return F.interpolate(x, size=size, mode="bilinear", align_corners=self.align_corners)
 
     _packs = None
@@ -368,17 +368,39 @@ class UPerHead(nn.Module):
         laterals and the top-down sums.  Returns the laterals, finest first, the last one the bottleneck's output."""
         inputs = [inputs[i] for i in self.in_index]
         x = inputs[-1]
-        psp = torch.cat([x] + [self._resize(m(x), x.shape[2:]) for m in self.psp_modules], dim=1)
+        pooled = [m(x) for m in self.psp_modules]
+        if self._records_own([x] + pooled):                                 # training: the resizes back + the concatenation, one kernel each way
+            psp = fused.resize_concat([x] + pooled)
+        else:
+            psp = torch.cat([x] + [self._resize(t, x.shape[2:]) for t in pooled], dim=1)
         laterals = [conv(inputs[i]) for i, conv in enumerate(self.lateral_convs)] + [self.bottleneck(psp)]
         for i in range(len(laterals) - 1, 0, -1):
-            laterals[i - 1] = laterals[i - 1] + self._resize(laterals[i], laterals[i - 1].shape[2:])
+            fine, coarse = laterals[i - 1], laterals[i]
+            if fine.shape[2] == 2 * coarse.shape[2] and fine.shape[3] == 2 * coarse.shape[3] and self._records_own([fine, coarse]):
+                laterals[i - 1] = fused.upsample2x_add(fine, coarse)        # training: the resize and the sum in one kernel
+            else:
+                laterals[i - 1] = fine + self._resize(coarse, fine.shape[2:])
         return laterals
+
+    def _records_own(self, levels):
+        """Whether a resize + sum / resize + concatenation of these tensors is recorded on the build's NHWC kernels (fused.upsample2x_add,
+        fused.resize_concat and their backward entries): only while autograd records — inference keeps its path — on the GPU, under
+        the conditions _mfma_top_down / _forward_mfma apply (_own_resize, at most 8 levels, channels a multiple of 8, no level larger than
+        the first) and with PPNET_LIBRARY_UPSAMPLE unset.  The kernels read NHWC: a level that is not channels_last is copied once, as
+        _forward_mfma's .contiguous(memory_format=channels_last) does."""
+        t0 = levels[0]
+        return (fused.recording(*levels) and not fused.library_upsample() and self._own_resize() and len(levels) <= 8
+                and t0.dtype in (torch.float32, torch.bfloat16)
+                and all(t.is_cuda and t.dtype == t0.dtype and t.shape[1] % 8 == 0 and t.shape[2] <= t0.shape[2] and t.shape[3] <= t0.shape[3]
+                        for t in levels))
 
     def forward(self, inputs):
         if self._prepared_mfma(inputs[self.in_index[-1]]):
             return self._forward_mfma(inputs)
         laterals = self._top_down(inputs)
         outs = [self.fpn_convs[i](laterals[i]) for i in range(len(laterals) - 1)] + [laterals[-1]]
+        if self._records_own(outs):                                         # training: the three resizes + the concatenation, one kernel each way
+            return self.conv_seg(self.fpn_bottleneck(fused.resize_concat(outs)))
         outs = [outs[0]] + [self._resize(o, outs[0].shape[2:]) for o in outs[1:]]
         return self.conv_seg(self.fpn_bottleneck(torch.cat(outs, dim=1)))
 
@@ -435,8 +457,8 @@ class UPerPUPHead(UPerHead):
                     t = step[1](t)
             ends.append(t)
         if (t.is_cuda and t.dtype in (torch.float32, torch.bfloat16) and self._chains_x2(t.shape[1])
-                and not fused.recording(t) and len({tuple(e.shape) for e in ends}) == 1):
-            cat = fused.upsample2x_concat(ends)                             # the last Upsample of every chain + torch.cat: one kernel
+                and len({tuple(e.shape) for e in ends}) == 1):
+            cat = fused.upsample2x_concat(ends)                             # the last Upsample of every chain + torch.cat: one kernel (it records its own backward)
         else:
             cat = torch.cat([chain[-1][1](e) if len(chain) else e for chain, e in zip(self.fpn_convs, ends)], dim=1)
         return self.conv_seg(self.dropout(self.fpn_bottleneck(cat)))        # cls_seg, decode_head.py:224-229
