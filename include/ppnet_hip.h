@@ -71,7 +71,8 @@ extern "C" {
  * 111 too, and so did ppn_seg_eval and ppn_augment_params / ppn_augment_codes / ppn_augment_rgb: new symbols change no existing
  * argument list and remove nothing, which is all the version guards against.  ppn_ohem_ce_workspace, ppn_ohem_ce_fwd and
  * ppn_ohem_ce_bwd joined at 111 in the same way, and so did ppn_resize_dice_workspace, ppn_resize_dice_fwd and ppn_resize_dice_bwd, and
- * ppn_upsample2x_nhwc_bwd, ppn_upsample2x_concat_nhwc_bwd and ppn_resize_concat_nhwc_bwd. */
+ * ppn_upsample2x_nhwc_bwd, ppn_upsample2x_concat_nhwc_bwd and ppn_resize_concat_nhwc_bwd, and ppn_residual_layernorm_train_fwd,
+ * ppn_residual_layernorm_bwd_workspace and ppn_residual_layernorm_bwd. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -521,6 +522,35 @@ int ppn_layernorm_offset(const void* x, const float* xoff, const void* w, const 
 int ppn_residual_layernorm_padded(const void* x, const void* a, const void* gamma, const void* w, const void* b,
                                   void* x_out, void* y_out, int64_t rows, int32_t C, float eps, int32_t dtype,
                                   int32_t Hr, int32_t Wr, int32_t Hp, int32_t Wp, void* stream);
+
+/* The TRAINING pair of ppn_residual_layernorm (csrc/residual_ln_bwd.hip): stochastic depth folded in, row statistics kept, and the
+ * backward of all of it in one pass over the rows.
+ *
+ * ppn_residual_layernorm_train_fwd:
+ *   a != NULL : x_out = x + scale[b] * gamma * a  (gamma NULL = 1; scale NULL = 1);  y_out = LayerNorm(x_out) unless y_out is NULL
+ *   a == NULL : y_out = LayerNorm(x)                                                  (x_out, gamma, scale ignored)
+ * scale [rows / rows_per_image] float32: image b owns rows_per_image consecutive rows; 0 drops the image's branch, 1 / keep scales
+ * it (timm's DropPath).  With y_out, stats [rows][2] float32 receives (mean, rstd) of every row; without, nothing is written to it.
+ * For bfloat16 the LayerNorm sees the rounded x_out.  x_out must not alias x when autograd keeps x.
+ *
+ * ppn_residual_layernorm_bwd: gy = the gradient at y_out (NULL: none, or no LayerNorm), gx = the gradient that arrives at x_out from
+ * its other consumers (NULL: none); at least one is given.  xn = the forward's x_out (x for a plain LayerNorm), stats its statistics
+ * (both needed with gy only).  With xhat = (xn - mean) rstd, g = gy w, G = gx + rstd (g - mean_c(g) - xhat mean_c(g xhat)):
+ *   dx = G        da = scale[b] gamma G        dgamma_c = sum_rows scale[b] a G        dw_c = sum_rows gy xhat        dbeta_c = sum_rows gy
+ * Every output pointer may be NULL (not wanted) except dx with gy; dgamma needs a and gamma, dw / dbeta need gy.  dx, da are rows x C
+ * of `dtype`, dgamma / dw / dbeta [C] of `dtype`: summed in float32 without atomics (one partial per workgroup in `workspace`, added
+ * in a fixed order by a second kernel) and rounded once, so two calls give the same bits.  workspace holds
+ * ppn_residual_layernorm_bwd_workspace(rows, C) floats (< 0: a width the kernels do not take).
+ *
+ * Widths as ppn_residual_layernorm.  PPN_E_INVALID before any HIP call for a NULL required pointer, rows <= 0, a dtype outside {0, 1},
+ * rows % rows_per_image != 0 with a scale, a workspace that is too small; PPN_E_UNSUPPORTED for another width or 2^31 rows and more. */
+int64_t ppn_residual_layernorm_bwd_workspace(int64_t rows, int32_t C);
+int ppn_residual_layernorm_train_fwd(const void* x, const void* a, const void* gamma, const float* scale, const void* w, const void* b,
+                                     void* x_out, void* y_out, float* stats, int64_t rows, int64_t rows_per_image, int32_t C, float eps,
+                                     int32_t dtype, void* stream);
+int ppn_residual_layernorm_bwd(const void* gy, const void* gx, const void* xn, const void* a, const void* gamma, const float* scale,
+                               const void* w, const float* stats, void* dx, void* da, void* dgamma, void* dw, void* dbeta, float* workspace,
+                               int64_t workspace_floats, int64_t rows, int64_t rows_per_image, int32_t C, int32_t dtype, void* stream);
 
 /* Bilinear x2 up-sampling of an NHWC tensor x [B][H][W][C] -> y [B][2H][2W][C] with PyTorch's
  * F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) arithmetic (the SETR-UP head's Upsample,

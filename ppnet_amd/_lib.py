@@ -60,7 +60,8 @@ EXPORTS = ("ppn_version", "ppn_error_string", "ppn_last_hip_error", "ppn_polyfit
            "ppn_augment_params", "ppn_augment_codes", "ppn_augment_rgb",
            "ppn_ohem_ce_workspace", "ppn_ohem_ce_fwd", "ppn_ohem_ce_bwd",
            "ppn_resize_dice_workspace", "ppn_resize_dice_fwd", "ppn_resize_dice_bwd",
-           "ppn_upsample2x_nhwc_bwd", "ppn_upsample2x_concat_nhwc_bwd", "ppn_resize_concat_nhwc_bwd")
+           "ppn_upsample2x_nhwc_bwd", "ppn_upsample2x_concat_nhwc_bwd", "ppn_resize_concat_nhwc_bwd",
+           "ppn_residual_layernorm_train_fwd", "ppn_residual_layernorm_bwd_workspace", "ppn_residual_layernorm_bwd")
 
 
 def _load():
@@ -138,6 +139,10 @@ def _load():
     lib.ppn_upsample2x_nhwc_bwd.argtypes = [_p, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
     lib.ppn_upsample2x_concat_nhwc_bwd.argtypes = [_p, C.POINTER(_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
     lib.ppn_resize_concat_nhwc_bwd.argtypes = [_p, C.POINTER(_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, _p]
+    lib.ppn_residual_layernorm_train_fwd.argtypes = [_p] * 9 + [C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_int32, _p]
+    lib.ppn_residual_layernorm_bwd_workspace.argtypes = [C.c_int64, C.c_int32]
+    lib.ppn_residual_layernorm_bwd_workspace.restype = C.c_int64
+    lib.ppn_residual_layernorm_bwd.argtypes = [_p] * 14 + [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _p]
     lib.ppn_grid_to_image.argtypes = [_p, _p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, _p]
     lib.ppn_seg_labels_2class.argtypes = [_p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
     lib.ppn_bias_act_nhwc.argtypes = [_p, _p, C.c_int64, C.c_int32, C.c_float, C.c_int32, _p]
@@ -187,7 +192,7 @@ def _load():
     for name in EXPORTS:
         getattr(lib, name)
         if name not in ("ppn_error_string", "ppn_na2d_bwd_workspace", "ppn_na2d_bwd_vpad_workspace", "ppn_mhsa_bwd_workspace", "ppn_swin_wmsa_bwd_workspace",
-                        "ppn_resize_ce_workspace", "ppn_ohem_ce_workspace", "ppn_resize_dice_workspace"):
+                        "ppn_resize_ce_workspace", "ppn_ohem_ce_workspace", "ppn_resize_dice_workspace", "ppn_residual_layernorm_bwd_workspace"):
             getattr(lib, name).restype = C.c_int
     return lib
 

@@ -663,6 +663,44 @@ int ppn_layernorm_offset(const void* x, const float* xoff, const void* w, const 
     return PPN_OK;
 }
 
+int64_t ppn_residual_layernorm_bwd_workspace(int64_t rows, int32_t C) {
+    return ppn::residual_ln_bwd_workspace_floats(rows, C);
+}
+
+int ppn_residual_layernorm_train_fwd(const void* x, const void* a, const void* gamma, const float* scale, const void* w, const void* b, void* x_out,
+                                     void* y_out, float* stats, int64_t rows, int64_t rows_per_image, int32_t C, float eps, int32_t dtype,
+                                     void* stream) {
+    if (!x || rows <= 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;
+    if (a ? !x_out : !y_out) return PPN_E_INVALID;                           // nothing to write
+    if (y_out && (!w || !b || !stats)) return PPN_E_INVALID;
+    if (scale && (rows_per_image <= 0 || rows % rows_per_image != 0)) return PPN_E_INVALID;
+    if (ppn::residual_ln_bwd_workspace_floats(rows, C) < 0) return PPN_E_UNSUPPORTED;      // the width (or 2^31 rows and more)
+    const int e = ppn::residual_ln_train_fwd_launch(x, a, gamma, scale, w, b, x_out, y_out, stats, rows, scale ? rows_per_image : 1, C, eps, dtype,
+                                                    (hipStream_t)stream);
+    if (e == -1) return PPN_E_UNSUPPORTED;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_residual_layernorm_bwd(const void* gy, const void* gx, const void* xn, const void* a, const void* gamma, const float* scale, const void* w,
+                               const float* stats, void* dx, void* da, void* dgamma, void* dw, void* dbeta, float* workspace,
+                               int64_t workspace_floats, int64_t rows, int64_t rows_per_image, int32_t C, int32_t dtype, void* stream) {
+    if ((!gy && !gx) || !workspace || rows <= 0 || (dtype != 0 && dtype != 1)) return PPN_E_INVALID;
+    if (gy && (!xn || !stats || !w || !dx)) return PPN_E_INVALID;            // the LayerNorm term needs its inputs and changes dx
+    if (dgamma && (!a || !gamma)) return PPN_E_INVALID;
+    if ((dw || dbeta) && !gy) return PPN_E_INVALID;
+    if (!dx && !da && !dgamma) return PPN_E_INVALID;                         // nothing to write
+    if (scale && (rows_per_image <= 0 || rows % rows_per_image != 0)) return PPN_E_INVALID;
+    const long long need = ppn::residual_ln_bwd_workspace_floats(rows, C);
+    if (need < 0) return PPN_E_UNSUPPORTED;                                  // the width (or 2^31 rows and more)
+    if (workspace_floats < need) return PPN_E_INVALID;
+    const int e = ppn::residual_ln_bwd_launch(gy, gx, xn, stats, dgamma ? a : nullptr, gamma, scale, w, dx, da, dgamma, dw, dbeta, workspace, rows,
+                                              scale ? rows_per_image : 1, C, dtype, (hipStream_t)stream);
+    if (e == -1) return PPN_E_UNSUPPORTED;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_upsample2x_nhwc(const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t relu, int32_t dtype,
                         void* stream) {
     return ppn_upsample2x_nhwc_bias(x, nullptr, y, B, H, W, C, relu, dtype, stream);

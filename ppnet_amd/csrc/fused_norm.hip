@@ -9,43 +9,9 @@
 #include <hip/hip_bf16.h>
 #include "ppn_device.h"
 #include "ppn_kernels.h"
+#include "norm_vec.h"
 
 namespace ppn {
-
-namespace {
-
-template <typename T> struct Vec8;
-template <> struct Vec8<float> {
-    static __device__ __forceinline__ void load(const float* p, float (&v)[8]) {
-        const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    }
-    static __device__ __forceinline__ void store(float* p, const float (&v)[8]) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-        *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    }
-};
-template <> struct Vec8<__hip_bfloat16> {
-    static __device__ __forceinline__ void load(const __hip_bfloat16* p, float (&v)[8]) {
-        const uint4 u = *reinterpret_cast<const uint4*>(p);
-        v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
-        v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
-        v[4] = __uint_as_float(u.z << 16); v[5] = __uint_as_float(u.z & 0xffff0000u);
-        v[6] = __uint_as_float(u.w << 16); v[7] = __uint_as_float(u.w & 0xffff0000u);
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) { return pack_bf16x2(lo, hi); }
-    static __device__ __forceinline__ void store(__hip_bfloat16* p, const float (&v)[8]) {
-        *reinterpret_cast<uint4*>(p) = make_uint4(pack(v[0], v[1]), pack(v[2], v[3]), pack(v[4], v[5]), pack(v[6], v[7]));
-    }
-};
-
-// sum over the `lpr` lanes that share a row (lpr a power of two <= 64, groups aligned)
-__device__ __forceinline__ float group_sum(float v, int lpr) {
-    for (int o = lpr >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-}  // namespace
 
 constexpr int NORM_ROW_ITERS = 8;     // row groups per wave: the per-channel vectors (w, b, offset: 5x the bytes of a bf16 row piece) are loaded once
 

@@ -124,6 +124,15 @@ int na2d_bwd_vpad_launch(const void* qkv, const void* pad_kv, const float* rpb, 
 int norm_launch(const void* x, const void* a, const void* gamma, const void* w, const void* b, void* x_out, void* y_out,
                 long long rows, int C, float eps, int dtype, int Hr, int Wr, int Hp, int Wp, const void* xoff, hipStream_t stream);
 
+// residual_ln_bwd.hip: the training pair of norm_launch's residual form (scale [rows / rows_per_image] float32 or null; -1 = a width the
+// kernels do not take; the workspace holds residual_ln_bwd_workspace_floats(rows, C) floats)
+long long residual_ln_bwd_workspace_floats(long long rows, int C);
+int residual_ln_train_fwd_launch(const void* x, const void* a, const void* gamma, const float* scale, const void* w, const void* b, void* x_out,
+                                 void* y_out, float* stats, long long rows, long long rows_per_image, int C, float eps, int dtype, hipStream_t stream);
+int residual_ln_bwd_launch(const void* gy, const void* gx, const void* xn, const float* stats, const void* a, const void* gamma, const float* scale,
+                           const void* w, void* dx, void* da, void* dgamma, void* dw, void* dbeta, float* workspace, long long rows,
+                           long long rows_per_image, int C, int dtype, hipStream_t stream);
+
 int resize_concat_launch(const void* const* x, const int* hw, const int* ch, int n, void* out, int B, int dtype, hipStream_t stream);
 int adaptive_pools_launch(const void* x, void* const* y, const int* scales, int n, int B, int H, int W, int C, int dtype, hipStream_t stream);
 int upsample2x_launch(const void* x, const void* bias, const void* add, void* y, int B, int H, int W, int C, int relu, int dtype, hipStream_t stream);

@@ -1,7 +1,9 @@
 """Host side of the fused residual / LayerScale / LayerNorm kernel (ppn_residual_layernorm). GPU only.
 
-Inference runs the HIP kernels below.  When autograd is recording (a training step, ppnet_amd/train.py) the same functions
-compose differentiable torch ops instead — the fused kernels are forward-only; the hand-written backwards are the
+Inference runs the HIP kernels below.  When autograd is recording (a training step, ppnet_amd/train.py) layer_norm and
+residual_layer_norm record the training pair of the same kernel (ppn_residual_layernorm_train_fwd / ppn_residual_layernorm_bwd,
+_ResidualLayerNormFunction: stochastic depth, LayerScale, the residual add, the next LayerNorm and the backward of all of it), and
+the functions without a backward kernel compose differentiable torch ops instead.  The other hand-written backwards are the
 attentions': neighbourhood (ppn_na2d_bwd, na.na2d_autograd), ViT's global one (ppn_mhsa_bwd, vit.mhsa_autograd) and Swin's window one
 (ppn_swin_wmsa_bwd, swin.wmsa_autograd) — the heads' loss: bilinear resize + cross-entropy (ppn_resize_ce_bwd,
 resize_cross_entropy below) — and the heads' bilinear up-sampling (ppn_upsample2x_nhwc_bwd, ppn_upsample2x_concat_nhwc_bwd,
@@ -110,11 +112,126 @@ def _layer_norm_autograd(x, ln, pad_to, offset):
     return y
 
 
+NORM_CALLS = {"fwd": 0, "bwd": 0}        # launches of ppn_residual_layernorm_train_fwd / ppn_residual_layernorm_bwd (like LOSS_CALLS)
+NORM_WIDTHS = frozenset(range(8, 65, 8)) | {128, 256, 512, 1024}          # csrc/residual_ln_bwd.hip: rln_geometry
+
+
+# Elements from which a PLAIN layer_norm records the kernel pair.  Below, the library's LayerNorm is two framework ops each way whose
+# dispatch costs less host time than one Python autograd node, three launches and a workspace, and the tensor is too small for the
+# kernels' bandwidth to pay that back (tools/residual_ln_timing.py, DESIGN.md section 22: 3.4x faster at 16.8 M elements, level to
+# 0.65x at 8.4 M, 0.62-0.66x at 4.2 M and 2.1 M in both dtypes).  residual_layer_norm replaces four to six framework ops each way and
+# was faster on every level shape: no gate.
+NORM_RECORD_MIN = 1 << 24
+
+
+def library_norm():
+    """PPNET_LIBRARY_NORM=1 (read at call time, like PPNET_LIBRARY_UPSAMPLE): while autograd records, layer_norm and residual_layer_norm
+    take the library composition (the DropPath multiply, gamma *, +, F.layer_norm and the framework's backwards) instead of the HIP
+    pair.  Inference is untouched."""
+    return bool(os.environ.get("PPNET_LIBRARY_NORM"))
+
+
+def _norm_kernels_record(x, a, gamma, ln, scale):
+    """Whether _ResidualLayerNormFunction takes these tensors while autograd records: CUDA, float32 / bfloat16, the branch and the
+    parameters of the activation's dtype, a width the kernels take (NORM_WIDTHS: not ViT-B's 768), a float32 scale per image, and the
+    knob off.  Everything else keeps the library composition."""
+    if library_norm() or not x.is_cuda or x.dtype not in _DT or x.dim() < 2 or x.numel() == 0 or x.shape[-1] not in NORM_WIDTHS:
+        return False
+    if ln is not None and (tuple(ln.normalized_shape) != (x.shape[-1],) or ln.weight is None or ln.bias is None):
+        return False
+    params = (gamma,) + ((ln.weight, ln.bias) if ln is not None else ())
+    if any(t is not None and (t.dtype != x.dtype or t.device != x.device or t.numel() != x.shape[-1]) for t in params):
+        return False
+    if a is not None and (a.dtype != x.dtype or a.device != x.device or a.shape != x.shape):
+        return False
+    return scale is None or (a is not None and scale.dtype == torch.float32 and scale.device == x.device and scale.dim() == 1
+                             and scale.numel() == x.shape[0] and not scale.requires_grad)
+
+
+def _rln_fwd(x, a, gamma, scale, w, b, eps):
+    """ppn_residual_layernorm_train_fwd on contiguous tensors: (x' — x itself for a plain LayerNorm —, y or None, stats or None)."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    x_out = torch.empty_like(x) if a is not None else None
+    y = torch.empty_like(x) if w is not None else None
+    stats = torch.empty(rows, 2, dtype=torch.float32, device=x.device) if w is not None else None
+    with torch.cuda.device(x.device):
+        rc = L.lib.ppn_residual_layernorm_train_fwd(_p(x), _p(a), _p(gamma), _p(scale), _p(w), _p(b), _p(x_out), _p(y), _p(stats), rows,
+                                                    rows // x.shape[0], C, float(eps), _DT[x.dtype], _stream(x))
+    L.check(rc, "ppn_residual_layernorm_train_fwd")
+    NORM_CALLS["fwd"] += 1
+    return (x_out if a is not None else x), y, stats
+
+
+def _rln_bwd(gy, gx, xn, stats, a, gamma, scale, w, want_dx, want_da, want_dgamma, want_dwb):
+    """ppn_residual_layernorm_bwd on contiguous tensors: (dx, da, dgamma, dw, dbeta), None where not wanted."""
+    ref = gy if gy is not None else gx
+    C = ref.shape[-1]
+    rows = ref.numel() // C
+    dx = torch.empty_like(ref) if want_dx else None
+    da = torch.empty_like(ref) if want_da else None
+    dgamma = torch.empty_like(gamma) if want_dgamma else None
+    dw, dbeta = (torch.empty_like(w), torch.empty_like(w)) if want_dwb else (None, None)
+    need = L.lib.ppn_residual_layernorm_bwd_workspace(rows, C)
+    ws = torch.empty(max(need, 1), dtype=torch.float32, device=ref.device)
+    with torch.cuda.device(ref.device):
+        rc = L.lib.ppn_residual_layernorm_bwd(_p(gy), _p(gx), _p(xn), _p(a), _p(gamma), _p(scale), _p(w), _p(stats), _p(dx), _p(da), _p(dgamma),
+                                              _p(dw), _p(dbeta), _p(ws), need, rows, rows // ref.shape[0], C, _DT[ref.dtype], _stream(ref))
+    L.check(rc, "ppn_residual_layernorm_bwd")
+    NORM_CALLS["bwd"] += 1
+    return dx, da, dgamma, dw, dbeta
+
+
+class _ResidualLayerNormFunction(torch.autograd.Function):
+    """x' = x + scale[b] * gamma * a, y = LayerNorm(x') on ppn_residual_layernorm_train_fwd / ppn_residual_layernorm_bwd: two outputs
+    (x', y), y None without a LayerNorm; a None = a plain LayerNorm, whose single output is y.  Saved: x' and the row statistics
+    (with a LayerNorm), the LayerNorm weight, gamma and scale when given, and a when gamma is given (dgamma is its only reader).  y is
+    not saved.  A gradient that does not arrive stays None and reaches the kernel as NULL."""
+
+    @staticmethod
+    def forward(ctx, x, a, gamma, scale, w, b, eps):
+        ctx.set_materialize_grads(False)
+        x = x.contiguous()
+        a = a.contiguous() if a is not None else None
+        gamma, w, b = (t.detach().contiguous() if t is not None else None for t in (gamma, w, b))
+        xn, y, stats = _rln_fwd(x, a, gamma, scale, w, b, eps)
+        ctx.plain, ctx.has_ln, ctx.has_gamma, ctx.has_scale = a is None, w is not None, gamma is not None, scale is not None
+        ctx.save_for_backward(*([xn, stats, w] if ctx.has_ln else []), *([gamma, a] if ctx.has_gamma else []), *([scale] if ctx.has_scale else []))
+        return y if ctx.plain else (xn, y)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        gx, gy = (None, grads[0]) if ctx.plain else grads
+        saved = list(ctx.saved_tensors)
+        xn, stats, w = (saved.pop(0), saved.pop(0), saved.pop(0)) if ctx.has_ln else (None, None, None)
+        gamma, a = (saved.pop(0), saved.pop(0)) if ctx.has_gamma else (None, None)
+        scale = saved.pop(0) if ctx.has_scale else None
+        need_x, need_a, need_gamma, _, need_w, need_b, _ = ctx.needs_input_grad
+        if gx is None and gy is None:
+            return (None,) * 7
+        gx, gy = (t.contiguous() if t is not None else None for t in (gx, gy))
+        # da is dx unless LayerScale or stochastic depth scales the branch; without a LayerNorm term dx is gx itself
+        own_da = need_a and (ctx.has_gamma or ctx.has_scale)
+        own_dx = gy is not None and (need_x or (need_a and not own_da))
+        want_dgamma, want_dwb = need_gamma and ctx.has_gamma, gy is not None and (need_w or need_b)
+        if own_dx or own_da or want_dgamma or want_dwb:
+            dx, da, dgamma, dw, dbeta = _rln_bwd(gy, gx, xn, stats, a, gamma, scale, w, gy is not None, own_da, want_dgamma, want_dwb)
+        else:
+            dx = da = dgamma = dw = dbeta = None
+        if gy is None:
+            dx = gx
+        return (dx if need_x else None, (da if own_da else dx) if need_a else None, dgamma, None, dw if need_w else None,
+                dbeta if need_b else None, None)
+
+
 def layer_norm(x, ln, pad_to=None, offset=None):
     """y = ln(x) for a torch.nn.LayerNorm over the last dimension. pad_to=(Hp,Wp): x is [B,H,W,C] and y is the
     zero-padded (bottom/right) [B,Hp,Wp,C] grid the next neighbourhood attention wants.  offset [C]: y = ln(x + offset)
     (a residual stream whose constant part is carried outside the tensor, ppn_layernorm_offset)."""
     if recording(x, ln.weight, ln.bias):
+        if pad_to is None and offset is None and x.numel() >= NORM_RECORD_MIN and _norm_kernels_record(x, None, None, ln, None):
+            return _ResidualLayerNormFunction.apply(x, None, None, None, ln.weight, ln.bias, ln.eps)
         return _layer_norm_autograd(x, ln, pad_to, offset)
     x = x.contiguous()
     if offset is not None:
@@ -152,12 +269,21 @@ def layer_norm_any_width(x, ln):
     return F.layer_norm(x, ln.normalized_shape, ln.weight, ln.bias, ln.eps)
 
 
-def residual_layer_norm(x, a, gamma, ln_next, pad_to=None):
-    """x' = x + gamma * a (gamma None = 1) in place of x; returns (x', ln_next(x')) — y is None when ln_next is None.
-    (Under autograd x' is a new tensor.)"""
+def residual_layer_norm(x, a, gamma, ln_next, pad_to=None, scale=None):
+    """x' = x + scale[b] * gamma * a (gamma None = 1; scale None = 1) in place of x; returns (x', ln_next(x')) — y is None when ln_next
+    is None.  scale: float32 [B], the per-image stochastic-depth factor (0 = dropped, 1 / keep otherwise) of a training step.
+    Under autograd x' is a new tensor and the HIP training pair is recorded (_ResidualLayerNormFunction); CPU tensors, mixed dtypes,
+    other widths, pad_to and PPNET_LIBRARY_NORM=1 compose the torch ops then."""
     if recording(x, a, gamma, *((ln_next.weight, ln_next.bias) if ln_next is not None else ())):
+        if pad_to is None and _norm_kernels_record(x, a, gamma, ln_next, scale):
+            w, b = (ln_next.weight, ln_next.bias) if ln_next is not None else (None, None)
+            return _ResidualLayerNormFunction.apply(x, a, gamma, scale, w, b, ln_next.eps if ln_next is not None else 0.0)
+        if scale is not None:                                               # the DropPath multiply (dense.drop_path) in the branch's dtype
+            a = a * scale.view((-1,) + (1,) * (a.dim() - 1)).to(a.dtype)
         x2 = x + (a if gamma is None else gamma * a)
         return x2, (_layer_norm_autograd(x2, ln_next, pad_to, None) if ln_next is not None else None)
+    if scale is not None:
+        a = a * scale.view((-1,) + (1,) * (a.dim() - 1)).to(a.dtype)
     x = x.contiguous()
     a = a.to(x.dtype).contiguous()
     y, pad = _y_for(x, pad_to) if ln_next is not None else (None, None)

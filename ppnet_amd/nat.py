@@ -10,7 +10,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import fused
-from .dense import IMG_MEAN, IMG_STD, accumulate, drop_path, library_width, linear, mfma_weights, use_mfma_conv
+from .dense import IMG_MEAN, IMG_STD, accumulate, library_width, linear, mfma_weights, use_mfma_conv
 from .na import NeighborhoodAttention2D
 
 
@@ -201,9 +201,20 @@ class NATLayer(nn.Module):
         if y is None:
             y = fused.layer_norm(x, self.norm1)
         real = hw if (y.shape[1], y.shape[2]) != hw else None               # a materialised padded y still works
-        dp = self.drop_path_rate if self.training else 0.0                  # x + drop_path(gamma * f(.)): the mask commutes with gamma
-        x, y2 = fused.residual_layer_norm(x, drop_path(self.attn(y, real), dp, self.training), self.gamma1 if self.layer_scale else None, self.norm2)
-        return fused.residual_layer_norm(x, drop_path(self.mlp(y2), dp, self.training), self.gamma2 if self.layer_scale else None, next_norm, next_pad)
+        # x + drop_path(gamma * f(.)): the mask commutes with gamma and rides into the residual kernel as a per-image scale
+        a = self.attn(y, real)
+        x, y2 = fused.residual_layer_norm(x, a, self.gamma1 if self.layer_scale else None, self.norm2, scale=self._drop_scale(a))
+        a = self.mlp(y2)
+        return fused.residual_layer_norm(x, a, self.gamma2 if self.layer_scale else None, next_norm, next_pad, scale=self._drop_scale(a))
+
+    def _drop_scale(self, a):
+        """Stochastic depth per sample (dense.drop_path's draw: the same call, shape, dtype and order, so a seeded run draws the same
+        masks) as the float32 [B] factor mask / keep of fused.residual_layer_norm; None in eval mode or at rate 0."""
+        if not self.training or self.drop_path_rate <= 0.0:
+            return None
+        keep = 1.0 - self.drop_path_rate
+        mask = a.new_empty((a.shape[0],) + (1,) * (a.dim() - 1)).bernoulli_(keep)
+        return (mask / keep).float().view(-1)
 
 
 def _fold_doc():

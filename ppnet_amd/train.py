@@ -13,9 +13,13 @@ mask_space / mask_path / the rendered map — the reference re-reads them from i
 neighbourhood attention's backward is the HIP kernel (ppn_na2d_bwd through na.na2d_autograd; ppn_na2d_bwd_vpad on the layers
 NATTEN pads to 7 * dilation, which train on their real tokens), so is the ViT backbone's global
 attention's (ppn_mhsa_bwd through vit.mhsa_autograd: no N x N tensor saved, bitwise-reproducible gradients), and the gradient
-exchange is torch's DistributedDataParallel over RCCL with buckets sized for xGMI rings (few large all-reduces).  Every other op
-of the backward pass is a ROCm library call through autograd: the fused inference kernels are forward-only and step aside while
-autograd is recording (fused.recording).
+exchange is torch's DistributedDataParallel over RCCL with buckets sized for xGMI rings (few large all-reduces).  The residual stream
+of the NAT / DiNAT blocks — stochastic depth, LayerScale, the residual add and the next LayerNorm — trains on the pair of its
+inference kernel (ppn_residual_layernorm_train_fwd / ppn_residual_layernorm_bwd through fused.residual_layer_norm; a bfloat16
+autocast step, whose stream is float32 with bfloat16 branches, keeps the library ops), the heads' loss and up-sampling on theirs
+(fused.resize_cross_entropy, fused.upsample2x_nhwc and its siblings).  The remaining ops of the backward pass (the projections, the
+convolutions, BatchNorm, GELU) are ROCm library calls through autograd: the other fused inference kernels are forward-only and step
+aside while autograd is recording (fused.recording).
 """
 import torch
 import torch.nn as nn
