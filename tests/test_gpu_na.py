@@ -1,6 +1,7 @@
 """GPU parity of the fused neighbourhood-attention kernel (C ABI ppn_na2d_fwd) and its nn.Module against the
 definition oracle (oracle/na_np.py; parity unpinned — NATTEN is not in the reference).  float32: 2e-5 absolute
-on O(1) outputs (fp32 accumulation order); bfloat16 I/O: 3e-2."""
+on O(1) outputs (fp32 accumulation order); bfloat16 I/O: 3e-2.
+Every kernel variant on its own (A/B knobs, known answers, large logits, guards): tests/test_gpu_na_variants.py."""
 import numpy as np
 import pytest
 
