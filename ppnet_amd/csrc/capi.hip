@@ -485,6 +485,12 @@ static bool resize_ce_sizes_ok(int B, int C, int h, int w, int H, int W) {
     return ppn_resize_ce_workspace(B, H, W) >= 0;
 }
 
+// work-items of a backward gather's launch: 1, 8 or 64 lanes per dlogit element in whole workgroups of `threads`, below 2^31
+static bool gather_launch_ok(int threads, int B, int C, int h, int w, int H, int W) {
+    const long long per = threads / ppn::resize_ce_bwd_lanes(h, w, H, W);
+    return (((long long)B * C * h * w + per - 1) / per) * threads < 0x7fffffffLL;
+}
+
 int ppn_resize_ce_fwd(const void* logit, const void* label, float* lse, float* loss, int64_t* correct, float* workspace, int64_t workspace_floats,
                       int B, int C, int h, int w, int H, int W, int ignore_index, int logit_dtype, int label_dtype, void* stream) {
     if (!logit || !label || !loss || !correct || !workspace) return PPN_E_INVALID;                    // lse may be NULL: no backward wanted
@@ -510,9 +516,7 @@ int ppn_resize_ce_bwd(const void* logit, const void* label, const float* lse, co
     if ((((uintptr_t)logit | (uintptr_t)lse | (uintptr_t)dlogit) & 15) != 0) return PPN_E_INVALID;
     if (((uintptr_t)grad_out & 3) != 0 || (label_dtype == 1 && ((uintptr_t)label & 7) != 0)) return PPN_E_INVALID;
     if (!resize_ce_sizes_ok(B, C, h, w, H, W)) return PPN_E_INVALID;
-    // work-items of the backward launch: 1, 8 or 64 lanes per dlogit element in whole workgroups
-    const long long per = ppn::resize_ce_threads() / ppn::resize_ce_bwd_lanes(h, w, H, W);
-    if ((((long long)B * C * h * w + per - 1) / per) * ppn::resize_ce_threads() >= 0x7fffffffLL) return PPN_E_INVALID;
+    if (!gather_launch_ok(ppn::resize_ce_threads(), B, C, h, w, H, W)) return PPN_E_INVALID;
     const int e = ppn::resize_ce_bwd_launch(logit, label, lse, grad_out, dlogit, B, C, h, w, H, W, ignore_index, logit_dtype, label_dtype,
                                             (hipStream_t)stream);
     if (e != 0) return hip_fail((hipError_t)e);
@@ -576,9 +580,7 @@ int ppn_ohem_ce_bwd(const void* logit, const void* label, const float* class_wei
     if (!threshold || !grad_out || !dlogit) return PPN_E_INVALID;
     if (!ohem_ce_common_ok(logit, label, class_weight, lse, score, B, C, h, w, H, W, mode, logit_dtype, label_dtype)) return PPN_E_INVALID;
     if (((uintptr_t)dlogit & 15) != 0 || (((uintptr_t)threshold | (uintptr_t)grad_out) & 3) != 0) return PPN_E_INVALID;
-    // work-items of the launch: 1, 8 or 64 lanes per dlogit element in whole workgroups
-    const long long per = ppn::ohem_ce_threads() / ppn::resize_ce_bwd_lanes(h, w, H, W);
-    if ((((long long)B * C * h * w + per - 1) / per) * ppn::ohem_ce_threads() >= 0x7fffffffLL) return PPN_E_INVALID;
+    if (!gather_launch_ok(ppn::ohem_ce_threads(), B, C, h, w, H, W)) return PPN_E_INVALID;
     const int e = ppn::ohem_ce_bwd_launch(logit, label, class_weight, lse, score, threshold, grad_out, dlogit, B, C, h, w, H, W, ignore_index, mode,
                                           logit_dtype, label_dtype, (hipStream_t)stream);
     if (e != 0) return hip_fail((hipError_t)e);
@@ -624,9 +626,7 @@ int ppn_resize_dice_bwd(const void* logit, const void* label, const float* lse, 
     if (!resize_dice_common_ok(logit, label, class_weight, workspace, lse, sums, B, C, h, w, H, W, smooth, logit_dtype, label_dtype))
         return PPN_E_INVALID;
     if (((uintptr_t)dlogit & 15) != 0 || ((uintptr_t)grad_out & 3) != 0) return PPN_E_INVALID;
-    // work-items of the gather: 1, 8 or 64 lanes per dlogit element in whole workgroups
-    const long long per = ppn::resize_dice_threads() / ppn::resize_ce_bwd_lanes(h, w, H, W);
-    if ((((long long)B * C * h * w + per - 1) / per) * ppn::resize_dice_threads() >= 0x7fffffffLL) return PPN_E_INVALID;
+    if (!gather_launch_ok(ppn::resize_dice_threads(), B, C, h, w, H, W)) return PPN_E_INVALID;
     const int e = ppn::resize_dice_bwd_launch(logit, label, lse, sums, class_weight, grad_out, workspace, dlogit, B, C, h, w, H, W, ignore_index,
                                               smooth, logit_dtype, label_dtype, (hipStream_t)stream);
     if (e != 0) return hip_fail((hipError_t)e);

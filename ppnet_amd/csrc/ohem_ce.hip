@@ -33,13 +33,18 @@
 //             ohem_reduce   finds the third digit — the key is complete, t is a float — and sums cw ce over the selected pixels per
 //                           workgroup in a fixed tree; writes mask when asked
 //             ohem_final    one workgroup: the partial sums in double / int64 in a fixed order; loss, counts, threshold
-//             ohem_bwd      resize_ce_bwd_kernel's gather (one writer per dlogit element, a fixed xor tree, no atomics) with the factor
-//                           (selected ? cw[label] : 0), `selected` recomputed from score and the device threshold
+//             ohem_bwd      resize_ce_bwd_kernel's gather (resize_tap.h's Gather: one writer per dlogit element, a fixed xor tree, no
+//                           atomics) with the factor (selected ? cw[label] : 0), `selected` recomputed from score and the device
+//                           threshold; a pixel that is not selected is skipped before its label is read
 //             Six launches and one memset forward (mode 0: four), one backward.  Every sum of floats has a fixed order and every
 //             atomic is an integer add: loss, threshold, mask and dlogit are bitwise reproducible.  Nothing is read back to the host.
 //
 // No kernel holds a runtime-C array (ScratchSize 0).  Element offsets are 64-bit; the caller (capi.hip) rejects B C h w, B H W and
 // launches of 2^31 or more.  n_valid <= B H W < 2^31 fits every uint32 bin and rank.
+//
+// What this file does as resize_ce.hip does is not copied but included (resize_tap.h): the taps, ohem_score's softmax_sweep,
+// ohem_reduce's group_sum, ohem_final's final_sum, ohem_bwd's Gather with tap_range and tap_weight, stf, and the host's dispatch_types
+// and dispatch_lanes.  Here stay the select (keys, histograms, select_bin), the score and the gather's per-pixel term.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
@@ -65,12 +70,6 @@ constexpr int OH_HIST2 = OH_BINS, OH_HIST3 = 2 * OH_BINS, OH_STATE = 3 * OH_BINS
 constexpr int OH_ST_VALID = 0, OH_ST_CORRECT = 1, OH_ST_BIN1 = 2, OH_ST_RANK1 = 3, OH_ST_BIN2 = 4, OH_ST_RANK2 = 5, OH_ST_THRESHOLD = 6;
 constexpr int OH_HEADER = OH_STATE + 16;               // zeroed on the stream by every forward call
 constexpr int OH_PARTIAL = OH_HEADER, OH_KEPT = OH_PARTIAL + OH_MAX_GROUPS, OH_WORDS = OH_KEPT + OH_MAX_GROUPS;
-
-template <typename T>
-__device__ __forceinline__ void stf(T* p, float v) {
-    if constexpr (sizeof(T) == 4) *p = v;
-    else *p = (__bf16)v;                                                                       // rounded to nearest even, once
-}
 
 __device__ __forceinline__ uint32_t score_key(float s) {
     const uint32_t u = __float_as_uint(s);
@@ -175,22 +174,14 @@ __global__ __launch_bounds__(OH_THREADS) void ohem_score_kernel(const T* __restr
                 const int r0 = ty.i0 * w, r1 = ty.i1 * w;
                 const T* img = logit + (size_t)b * C * plane;
                 const int lab = valid_label(label, (size_t)p, C, ignore_index);
-                float m = interp(img, r0, r1, ty, tx), zl = m;
-                int arg = 0;
-                for (int c = 1; c < C; ++c) {
-                    const float z = interp(img + c * plane, r0, r1, ty, tx);
-                    if (z > m) { m = z; arg = c; }                           // ties keep the lowest class
-                    if (c == lab) zl = z;
-                }
-                float s = 0.f;
-                for (int c = 0; c < C; ++c) s += expf(interp(img + c * plane, r0, r1, ty, tx) - m);
-                const float l = m + logf(s);
+                const Sweep sw = softmax_sweep(img, plane, C, r0, r1, ty, tx, lab);
+                const float l = sw.m + logf(sw.s);
                 lse[p] = l;
                 float sc = __uint_as_float(0x7fc00000u);                     // ignored: the NaN sentinel
                 if (lab >= 0) {
-                    sc = mode == 1 ? expf(zl - l) : (cw ? cw[lab] : 1.f) * (l - zl);
+                    sc = mode == 1 ? expf(sw.zl - l) : (cw ? cw[lab] : 1.f) * (l - sw.zl);
                     sc = (sc != sc) ? INFINITY : sc + 0.f;                   // a valid pixel is never NaN; -0 becomes +0
-                    correct += (arg == lab);
+                    correct += (sw.arg == lab);
                     n_valid += 1;
                     on = mode != 0;
                     key = score_key(sc);
@@ -302,21 +293,10 @@ __global__ __launch_bounds__(OH_THREADS) void ohem_reduce_kernel(const T* __rest
             kept += 1;
         }
     }
-    // fixed tree: xor shuffles within the wave, then the four waves in order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        loss += __shfl_xor(loss, o, 64);
-        kept += __shfl_xor(kept, o, 64);
-    }
-    if ((tid & 63) == 0) { s_loss[tid >> 6] = loss; s_kept[tid >> 6] = kept; }
-    __syncthreads();
+    const FloatInt sum = group_sum<OH_THREADS>(loss, kept, s_loss, s_kept);  // a fixed tree
     if (tid == 0) {
-        float a = s_loss[0];
-        int n = s_kept[0];
-#pragma unroll
-        for (int i = 1; i < OH_THREADS / 64; ++i) { a += s_loss[i]; n += s_kept[i]; }
-        reinterpret_cast<float*>(ws)[OH_PARTIAL + blockIdx.x] = a;
-        reinterpret_cast<int*>(ws)[OH_KEPT + blockIdx.x] = n;
+        reinterpret_cast<float*>(ws)[OH_PARTIAL + blockIdx.x] = sum.a;
+        reinterpret_cast<int*>(ws)[OH_KEPT + blockIdx.x] = sum.n;
     }
 }
 
@@ -331,41 +311,15 @@ __global__ __launch_bounds__(OH_THREADS) void ohem_final_kernel(const uint32_t* 
     double a = 0.0;
     long long n = 0;
     for (int i = tid; i < n_groups; i += OH_THREADS) { a += (double)part[i]; n += kept[i]; }
-    s_a[tid] = a;
-    s_n[tid] = n;
-    __syncthreads();
-    for (int o = OH_THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) { s_a[tid] += s_a[tid + o]; s_n[tid] += s_n[tid + o]; }
-        __syncthreads();
-    }
+    final_sum<OH_THREADS>(a, n, s_a, s_n);
     if (tid == 0) {
-        *loss = (float)(s_a[0] / n_px);
+        *loss = (float)(a / n_px);
         counts[0] = (long long)ws[OH_STATE + OH_ST_CORRECT];
         counts[1] = (long long)ws[OH_STATE + OH_ST_VALID];
-        counts[2] = s_n[0];
+        counts[2] = n;
         *threshold = __uint_as_float(ws[OH_STATE + OH_ST_THRESHOLD]);
     }
 }
-
-// resize_ce.hip's tap_range: first / last destination index in [0, n_out) whose taps touch source index y (first > last: none); the
-// scan decides membership with bilinear_tap itself, so rounding can neither drop nor double a pixel
-__device__ __forceinline__ void tap_range(int y, int n_in, int n_out, int& first, int& last) {
-    const double r = (double)n_out / (double)n_in;
-    const double lo = floor(((double)y - 0.5) * r - 0.5), hi = ceil(((double)y + 1.5) * r - 0.5);
-    const double margin = 1.0 + floor(hi * 1.0e-6);        // one, plus the float32 error of the source index (< 2.4e-7 of it)
-    const int c0 = (int)fmax(lo - margin, 0.0), c1 = (int)fmin(hi + margin, (double)(n_out - 1));
-    first = c1 + 1;
-    last = c0 - 1;
-    for (int Y = c0; Y <= c1; ++Y) {
-        const Tap t = bilinear_tap(Y, n_in, n_out);
-        if (t.i0 == y || t.i1 == y) {
-            if (first > c1) first = Y;
-            last = Y;
-        }
-    }
-}
-
-__device__ __forceinline__ float tap_weight(const Tap& t, int y) { return (t.i0 == y ? t.l0 : 0.f) + (t.i1 == y ? t.l1 : 0.f); }
 
 template <typename T, typename LT, int LANES>
 __global__ __launch_bounds__(OH_THREADS) void ohem_bwd_kernel(const T* __restrict__ logit, const LT* __restrict__ label,
@@ -373,39 +327,19 @@ __global__ __launch_bounds__(OH_THREADS) void ohem_bwd_kernel(const T* __restric
                                                                const float* __restrict__ score, const float* __restrict__ threshold,
                                                                const float* __restrict__ grad_out, T* __restrict__ dlogit, long long n_out, int C,
                                                                int h, int w, int H, int W, int ignore_index, int mode, float inv_px) {
-    constexpr int OUTS = OH_THREADS / LANES;               // outputs per workgroup
-    const int lane = threadIdx.x % LANES;
-    const long long o = (long long)blockIdx.x * OUTS + threadIdx.x / LANES;
-    const bool live = o < n_out;                           // the lanes of an output agree; no early return before the shuffles
+    const Gather<OH_THREADS, LANES> out(n_out, C, h, w);
+    const T* plane = logit + (size_t)out.bc * h * w;
     const float t = *threshold;
-    double acc = 0.0;                                      // a footprint of ~1000 signed terms that cancel: summed in double, rounded once
-    if (live) {
-        const int x = (int)(o % w), y = (int)((o / w) % h);
-        const int bc = (int)(o / ((long long)w * h)), b = bc / C, c = bc - b * C;
-        int Y0, Y1, X0, X1;
-        tap_range(y, h, H, Y0, Y1);
-        tap_range(x, w, W, X0, X1);
-        const int ny = Y1 - Y0 + 1, nx = X1 - X0 + 1;
-        if (ny > 0 && nx > 0) {
-            const T* plane = logit + (size_t)bc * h * w;
-            const size_t px0 = (size_t)b * H * W;
-            const int n = ny * nx;                         // < 2^31: a subset of one image's H W pixels
-            for (int i = lane; i < n; i += LANES) {
-                const int dy = i / nx, Y = Y0 + dy, X = X0 + (i - dy * nx);
-                const size_t p = px0 + (size_t)Y * W + X;
-                if (!selected(score[p], t, mode)) continue;
-                const int lab = valid_label(label, p, C, ignore_index);
-                if (lab < 0) continue;
-                const Tap ty = bilinear_tap(Y, h, H), tx = bilinear_tap(X, w, W);
-                const float z = interp(plane, ty.i0 * w, ty.i1 * w, ty, tx);
-                const float g = (cw ? cw[lab] : 1.f) * (expf(z - lse[p]) - (lab == c ? 1.f : 0.f));
-                acc += (double)(tap_weight(ty, y) * tap_weight(tx, x) * g);
-            }
-        }
-    }
-#pragma unroll
-    for (int s = LANES / 2; s > 0; s >>= 1) acc += __shfl_xor(acc, s, LANES);
-    if (live && lane == 0) stf(dlogit + o, (float)acc * (*grad_out * inv_px));
+    const double acc = out.sum(true, h, w, H, W, [&](double& sum, size_t p, int Y, int X) {
+        if (!selected(score[p], t, mode)) return;          // before the label is read
+        const int lab = valid_label(label, p, C, ignore_index);
+        if (lab < 0) return;
+        const Tap ty = bilinear_tap(Y, h, H), tx = bilinear_tap(X, w, W);
+        const float z = interp(plane, ty.i0 * w, ty.i1 * w, ty, tx);
+        const float g = (cw ? cw[lab] : 1.f) * (expf(z - lse[p]) - (lab == out.c ? 1.f : 0.f));
+        sum += (double)(tap_weight(ty, out.y) * tap_weight(tx, out.x) * g);   // a float32 product, rounded once, then widened
+    });
+    if (out.live && out.lane() == 0) stf(dlogit + out.o, (float)acc * (*grad_out * inv_px));
 }
 
 template <typename T, typename LT>
@@ -430,22 +364,15 @@ int fwd_typed(const void* logit, const void* label, const float* cw, float* lse,
     return (int)hipGetLastError();
 }
 
-template <typename T, typename LT, int LANES>
-void bwd_lanes(const void* logit, const void* label, const float* cw, const float* lse, const float* score, const float* threshold,
-               const float* grad_out, void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index, int mode, hipStream_t stream) {
-    const long long n_out = (long long)B * C * h * w, outs = OH_THREADS / LANES;
-    hipLaunchKernelGGL((ohem_bwd_kernel<T, LT, LANES>), dim3((unsigned)((n_out + outs - 1) / outs)), dim3(OH_THREADS), 0, stream, (const T*)logit,
-                       (const LT*)label, cw, lse, score, threshold, grad_out, (T*)dlogit, n_out, C, h, w, H, W, ignore_index, mode,
-                       1.0f / (float)((long long)B * H * W));
-}
-
 template <typename T, typename LT>
 int bwd_typed(const void* logit, const void* label, const float* cw, const float* lse, const float* score, const float* threshold,
               const float* grad_out, void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index, int mode, hipStream_t stream) {
-    const int lanes = resize_ce_bwd_lanes(h, w, H, W);     // resize_ce.hip's rule: the footprint of an output is the same
-    if (lanes == 1) bwd_lanes<T, LT, 1>(logit, label, cw, lse, score, threshold, grad_out, dlogit, B, C, h, w, H, W, ignore_index, mode, stream);
-    else if (lanes == 8) bwd_lanes<T, LT, 8>(logit, label, cw, lse, score, threshold, grad_out, dlogit, B, C, h, w, H, W, ignore_index, mode, stream);
-    else bwd_lanes<T, LT, 64>(logit, label, cw, lse, score, threshold, grad_out, dlogit, B, C, h, w, H, W, ignore_index, mode, stream);
+    const long long n_out = (long long)B * C * h * w;
+    dispatch_lanes(OH_THREADS, n_out, h, w, H, W, [&](auto lanes, dim3 grid) {
+        hipLaunchKernelGGL((ohem_bwd_kernel<T, LT, decltype(lanes)::value>), grid, dim3(OH_THREADS), 0, stream, (const T*)logit, (const LT*)label,
+                           cw, lse, score, threshold, grad_out, (T*)dlogit, n_out, C, h, w, H, W, ignore_index, mode,
+                           1.0f / (float)((long long)B * H * W));
+    });
     return (int)hipGetLastError();
 }
 }  // namespace
@@ -463,21 +390,19 @@ int ohem_ce_fwd_launch(const void* logit, const void* label, const float* class_
                        float* threshold, uint8_t* mask, void* workspace, int B, int C, int h, int w, int H, int W, int ignore_index, int mode,
                        float thresh, uint32_t batch_kept, int logit_dtype, int label_dtype, hipStream_t stream) {
     uint32_t* ws = (uint32_t*)workspace;
-#define PPN_OHEM_FWD(T, LT) \
-    fwd_typed<T, LT>(logit, label, class_weight, lse, score, loss, counts, threshold, mask, ws, B, C, h, w, H, W, ignore_index, mode, thresh, batch_kept, stream)
-    if (logit_dtype == 0) return label_dtype == 0 ? PPN_OHEM_FWD(float, uint8_t) : PPN_OHEM_FWD(float, int64_t);
-    return label_dtype == 0 ? PPN_OHEM_FWD(__bf16, uint8_t) : PPN_OHEM_FWD(__bf16, int64_t);
-#undef PPN_OHEM_FWD
+    return dispatch_types(logit_dtype, label_dtype, [&](auto t, auto lt) {
+        return fwd_typed<decltype(t), decltype(lt)>(logit, label, class_weight, lse, score, loss, counts, threshold, mask, ws, B, C, h, w, H, W,
+                                                    ignore_index, mode, thresh, batch_kept, stream);
+    });
 }
 
 int ohem_ce_bwd_launch(const void* logit, const void* label, const float* class_weight, const float* lse, const float* score, const float* threshold,
                        const float* grad_out, void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index, int mode, int logit_dtype,
                        int label_dtype, hipStream_t stream) {
-#define PPN_OHEM_BWD(T, LT) \
-    bwd_typed<T, LT>(logit, label, class_weight, lse, score, threshold, grad_out, dlogit, B, C, h, w, H, W, ignore_index, mode, stream)
-    if (logit_dtype == 0) return label_dtype == 0 ? PPN_OHEM_BWD(float, uint8_t) : PPN_OHEM_BWD(float, int64_t);
-    return label_dtype == 0 ? PPN_OHEM_BWD(__bf16, uint8_t) : PPN_OHEM_BWD(__bf16, int64_t);
-#undef PPN_OHEM_BWD
+    return dispatch_types(logit_dtype, label_dtype, [&](auto t, auto lt) {
+        return bwd_typed<decltype(t), decltype(lt)>(logit, label, class_weight, lse, score, threshold, grad_out, dlogit, B, C, h, w, H, W,
+                                                    ignore_index, mode, stream);
+    });
 }
 
 }  // namespace ppn

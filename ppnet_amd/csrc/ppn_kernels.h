@@ -172,7 +172,9 @@ long long swin_wmsa_bwd_workspace_floats(int heads);
 int swin_wmsa_bwd_launch(const void* qkv, const void* pad_kv, const float* rpb, const void* dout, void* dqkv, float* dpad_kv, float* drpb,
                          float* workspace, int B, int H, int W, int heads, int shift, float scale, int dtype, hipStream_t stream);
 // resize_ce.hip: bilinear resize + cross-entropy loss of a segmentation head, forward and backward; pixels per forward workgroup,
-// work-items per workgroup of every kernel, and the lanes that share one output of the backward (1 / 8 / 64 by the resize ratio)
+// work-items per workgroup of every kernel, and the lanes that share one output of the backward (1 / 8 / 64 by the resize ratio: the
+// rule of ohem_ce.hip's and resize_dice.hip's backward too).  What this file, seg_eval.hip, ohem_ce.hip and resize_dice.hip share —
+// taps, softmax sweep, reductions, the backward's gather, the dtype and lane dispatch — is inline code in resize_tap.h, not declared here
 int resize_ce_fwd_pixels();
 int resize_ce_threads();
 int resize_ce_bwd_lanes(int h, int w, int H, int W);
@@ -183,7 +185,7 @@ int resize_ce_bwd_launch(const void* logit, const void* label, const float* lse,
                          int H, int W, int ignore_index, int logit_dtype, int label_dtype, hipStream_t stream);
 // seg_eval.hip: bilinear resize + argmax + the three per-class area histograms of a segmentation evaluation; pixels per tile,
 // work-items per workgroup, the largest grid (a workgroup strides over the tiles) and the largest C (pred is uint8, the LDS
-// histogram is fixed)
+// histogram is fixed).  Taps and dtype dispatch: resize_tap.h; the argmax sweep (from -inf) is its own
 int seg_eval_pixels();
 int seg_eval_threads();
 int seg_eval_max_groups();
@@ -192,7 +194,8 @@ int seg_eval_launch(const void* logit, const void* label, uint8_t* pred, int64_t
                     int logit_dtype, int label_dtype, hipStream_t stream);
 // ohem_ce.hip: resize_ce.hip's loss with online hard example mining (a radix select of the k-th score) and class weights, forward and
 // backward; pixels per tile, work-items per workgroup, the largest grid (a workgroup strides over the tiles) and the workspace (bytes,
-// the same for every size).  mode 0 = no sampler, 1 = threshold on the label's probability, 2 = the batch_kept largest losses
+// the same for every size).  mode 0 = no sampler, 1 = threshold on the label's probability, 2 = the batch_kept largest losses.
+// Sweep, reductions and gather: resize_tap.h
 int ohem_ce_pixels();
 int ohem_ce_threads();
 int ohem_ce_max_groups();
@@ -204,7 +207,8 @@ int ohem_ce_bwd_launch(const void* logit, const void* label, const float* class_
                        const float* grad_out, void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index, int mode, int logit_dtype,
                        int label_dtype, hipStream_t stream);
 // resize_dice.hip: bilinear resize + Dice loss (mmseg's DiceLoss, exponent 2) of a segmentation head, forward and backward; pixels per
-// tile (a tile lies inside one image), work-items per workgroup, the largest C (LDS arrays are fixed) and the workspace in bytes
+// tile (a tile lies inside one image), work-items per workgroup, the largest C (LDS arrays are fixed) and the workspace in bytes.
+// Sweep, final reduction and gather: resize_tap.h
 int resize_dice_pixels();
 int resize_dice_threads();
 int resize_dice_max_classes();

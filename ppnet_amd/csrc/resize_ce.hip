@@ -28,6 +28,11 @@
 //
 // No kernel holds a runtime-C array: every one loops over the channels (ScratchSize 0).  Element offsets are 64-bit; the caller
 // (capi.hip) rejects B C h w, B H W and launches of 2^31 or more.
+//
+// What ohem_ce.hip and resize_dice.hip do the same way lives in resize_tap.h, once: the taps (Tap, bilinear_tap, ldf, stf, interp,
+// valid_label), the forward's softmax_sweep, group_sum and final_sum, the backward's tap_range, tap_weight and Gather, and the host's
+// dispatch_types and dispatch_lanes.  This file keeps its kernels, its constants and what is the cross-entropy's own: the loss term,
+// the gather's per-pixel term and its store.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
@@ -41,14 +46,6 @@ namespace {
 constexpr int RCE_THREADS = 256;                       // work-items per workgroup, every kernel
 constexpr int RCE_FWD_PER_THREAD = 4;
 constexpr int RCE_FWD_PX = RCE_THREADS * RCE_FWD_PER_THREAD;   // pixels per forward workgroup
-
-// Tap, bilinear_tap, ldf, interp and valid_label: resize_tap.h (shared with seg_eval.hip, whose argmax is this file's)
-
-template <typename T>
-__device__ __forceinline__ void stf(T* p, float v) {
-    if constexpr (sizeof(T) == 4) *p = v;
-    else *p = (__bf16)v;                                                                       // rounded to nearest even, once
-}
 
 template <typename T, typename LT>
 __global__ __launch_bounds__(RCE_THREADS) void resize_ce_fwd_kernel(const T* __restrict__ logit, const LT* __restrict__ label,
@@ -69,37 +66,18 @@ __global__ __launch_bounds__(RCE_THREADS) void resize_ce_fwd_kernel(const T* __r
         const int r0 = ty.i0 * w, r1 = ty.i1 * w;
         const T* img = logit + (size_t)b * C * plane;
         const int lab = valid_label(label, (size_t)p, C, ignore_index);
-        float m = interp(img, r0, r1, ty, tx), zl = m;
-        int arg = 0;
-        for (int c = 1; c < C; ++c) {
-            const float z = interp(img + c * plane, r0, r1, ty, tx);
-            if (z > m) { m = z; arg = c; }                         // ties keep the lowest class
-            if (c == lab) zl = z;
-        }
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) s += expf(interp(img + c * plane, r0, r1, ty, tx) - m);
-        const float l = m + logf(s);
+        const Sweep sw = softmax_sweep(img, plane, C, r0, r1, ty, tx, lab);
+        const float l = sw.m + logf(sw.s);
         if (lse) lse[p] = l;
         if (lab >= 0) {
-            loss += l - zl;
-            cnt += (arg == lab);
+            loss += l - sw.zl;
+            cnt += (sw.arg == lab);
         }
     }
-    // fixed tree: xor shuffles within the wave, then the four waves in order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        loss += __shfl_xor(loss, o, 64);
-        cnt += __shfl_xor(cnt, o, 64);
-    }
-    if ((tid & 63) == 0) { s_loss[tid >> 6] = loss; s_cnt[tid >> 6] = cnt; }
-    __syncthreads();
+    const FloatInt sum = group_sum<RCE_THREADS>(loss, cnt, s_loss, s_cnt);   // a fixed tree
     if (tid == 0) {
-        float a = s_loss[0];
-        int n = s_cnt[0];
-#pragma unroll
-        for (int i = 1; i < RCE_THREADS / 64; ++i) { a += s_loss[i]; n += s_cnt[i]; }
-        ws[blockIdx.x] = a;
-        reinterpret_cast<int*>(ws)[(size_t)n_groups + blockIdx.x] = n;
+        ws[blockIdx.x] = sum.a;
+        reinterpret_cast<int*>(ws)[(size_t)n_groups + blockIdx.x] = sum.n;
     }
 }
 
@@ -113,72 +91,26 @@ __global__ __launch_bounds__(RCE_THREADS) void resize_ce_final_kernel(const floa
     double a = 0.0;
     long long n = 0;
     for (int i = tid; i < n_groups; i += RCE_THREADS) { a += (double)ws[i]; n += cnt[i]; }
-    s_a[tid] = a;
-    s_n[tid] = n;
-    __syncthreads();
-    for (int o = RCE_THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) { s_a[tid] += s_a[tid + o]; s_n[tid] += s_n[tid + o]; }
-        __syncthreads();
-    }
-    if (tid == 0) { *loss = (float)(s_a[0] / n_px); *correct = s_n[0]; }
+    final_sum<RCE_THREADS>(a, n, s_a, s_n);
+    if (tid == 0) { *loss = (float)(a / n_px); *correct = n; }
 }
-
-// first / last destination index in [0, n_out) whose taps touch source index y (first > last: none).  The exact range is
-// ((y - 1 + 0.5) n_out / n_in - 0.5, (y + 1 + 0.5) n_out / n_in - 0.5); the scan decides membership with bilinear_tap itself.
-__device__ __forceinline__ void tap_range(int y, int n_in, int n_out, int& first, int& last) {
-    const double r = (double)n_out / (double)n_in;
-    const double lo = floor(((double)y - 0.5) * r - 0.5), hi = ceil(((double)y + 1.5) * r - 0.5);
-    const double margin = 1.0 + floor(hi * 1.0e-6);        // one, plus the float32 error of the source index (< 2.4e-7 of it)
-    const int c0 = (int)fmax(lo - margin, 0.0), c1 = (int)fmin(hi + margin, (double)(n_out - 1));
-    first = c1 + 1;
-    last = c0 - 1;
-    for (int Y = c0; Y <= c1; ++Y) {
-        const Tap t = bilinear_tap(Y, n_in, n_out);
-        if (t.i0 == y || t.i1 == y) {
-            if (first > c1) first = Y;
-            last = Y;
-        }
-    }
-}
-
-__device__ __forceinline__ float tap_weight(const Tap& t, int y) { return (t.i0 == y ? t.l0 : 0.f) + (t.i1 == y ? t.l1 : 0.f); }
 
 template <typename T, typename LT, int LANES>
 __global__ __launch_bounds__(RCE_THREADS) void resize_ce_bwd_kernel(const T* __restrict__ logit, const LT* __restrict__ label,
                                                                      const float* __restrict__ lse, const float* __restrict__ grad_out,
                                                                      T* __restrict__ dlogit, long long n_out, int C, int h, int w, int H,
                                                                      int W, int ignore_index, float inv_px) {
-    constexpr int OUTS = RCE_THREADS / LANES;              // outputs per workgroup
-    const int lane = threadIdx.x % LANES;
-    const long long o = (long long)blockIdx.x * OUTS + threadIdx.x / LANES;
-    const bool live = o < n_out;                           // the lanes of an output agree; no early return before the shuffles
-    double acc = 0.0;                                      // a footprint of ~1000 signed terms that cancel: summed in double, rounded once
-    if (live) {
-        const int x = (int)(o % w), y = (int)((o / w) % h);
-        const int bc = (int)(o / ((long long)w * h)), b = bc / C, c = bc - b * C;
-        int Y0, Y1, X0, X1;
-        tap_range(y, h, H, Y0, Y1);
-        tap_range(x, w, W, X0, X1);
-        const int ny = Y1 - Y0 + 1, nx = X1 - X0 + 1;
-        if (ny > 0 && nx > 0) {
-            const T* plane = logit + (size_t)bc * h * w;
-            const size_t px0 = (size_t)b * H * W;
-            const int n = ny * nx;                         // < 2^31: a subset of one image's H W pixels
-            for (int i = lane; i < n; i += LANES) {
-                const int dy = i / nx, Y = Y0 + dy, X = X0 + (i - dy * nx);
-                const size_t p = px0 + (size_t)Y * W + X;
-                const int lab = valid_label(label, p, C, ignore_index);
-                if (lab < 0) continue;
-                const Tap ty = bilinear_tap(Y, h, H), tx = bilinear_tap(X, w, W);
-                const float z = interp(plane, ty.i0 * w, ty.i1 * w, ty, tx);
-                const float g = expf(z - lse[p]) - (lab == c ? 1.f : 0.f);
-                acc += (double)(tap_weight(ty, y) * tap_weight(tx, x) * g);
-            }
-        }
-    }
-#pragma unroll
-    for (int s = LANES / 2; s > 0; s >>= 1) acc += __shfl_xor(acc, s, LANES);
-    if (live && lane == 0) stf(dlogit + o, (float)acc * (*grad_out * inv_px));
+    const Gather<RCE_THREADS, LANES> out(n_out, C, h, w);
+    const T* plane = logit + (size_t)out.bc * h * w;
+    const double acc = out.sum(true, h, w, H, W, [&](double& sum, size_t p, int Y, int X) {
+        const int lab = valid_label(label, p, C, ignore_index);
+        if (lab < 0) return;
+        const Tap ty = bilinear_tap(Y, h, H), tx = bilinear_tap(X, w, W);
+        const float z = interp(plane, ty.i0 * w, ty.i1 * w, ty, tx);
+        const float g = expf(z - lse[p]) - (lab == out.c ? 1.f : 0.f);
+        sum += (double)(tap_weight(ty, out.y) * tap_weight(tx, out.x) * g);   // a float32 product, rounded once, then widened
+    });
+    if (out.live && out.lane() == 0) stf(dlogit + out.o, (float)acc * (*grad_out * inv_px));
 }
 
 template <typename T, typename LT>
@@ -193,22 +125,14 @@ int fwd_typed(const void* logit, const void* label, float* lse, float* loss, int
     return (int)hipGetLastError();
 }
 
-template <typename T, typename LT, int LANES>
-void bwd_lanes(const void* logit, const void* label, const float* lse, const float* grad_out, void* dlogit, int B, int C, int h, int w, int H,
-               int W, int ignore_index, hipStream_t stream) {
-    const long long n_out = (long long)B * C * h * w, outs = RCE_THREADS / LANES;
-    hipLaunchKernelGGL((resize_ce_bwd_kernel<T, LT, LANES>), dim3((unsigned)((n_out + outs - 1) / outs)), dim3(RCE_THREADS), 0, stream,
-                       (const T*)logit, (const LT*)label, lse, grad_out, (T*)dlogit, n_out, C, h, w, H, W, ignore_index,
-                       1.0f / (float)((long long)B * H * W));
-}
-
 template <typename T, typename LT>
 int bwd_typed(const void* logit, const void* label, const float* lse, const float* grad_out, void* dlogit, int B, int C, int h, int w, int H, int W,
               int ignore_index, hipStream_t stream) {
-    const int lanes = resize_ce_bwd_lanes(h, w, H, W);
-    if (lanes == 1) bwd_lanes<T, LT, 1>(logit, label, lse, grad_out, dlogit, B, C, h, w, H, W, ignore_index, stream);
-    else if (lanes == 8) bwd_lanes<T, LT, 8>(logit, label, lse, grad_out, dlogit, B, C, h, w, H, W, ignore_index, stream);
-    else bwd_lanes<T, LT, 64>(logit, label, lse, grad_out, dlogit, B, C, h, w, H, W, ignore_index, stream);
+    const long long n_out = (long long)B * C * h * w;
+    dispatch_lanes(RCE_THREADS, n_out, h, w, H, W, [&](auto lanes, dim3 grid) {
+        hipLaunchKernelGGL((resize_ce_bwd_kernel<T, LT, decltype(lanes)::value>), grid, dim3(RCE_THREADS), 0, stream, (const T*)logit,
+                           (const LT*)label, lse, grad_out, (T*)dlogit, n_out, C, h, w, H, W, ignore_index, 1.0f / (float)((long long)B * H * W));
+    });
     return (int)hipGetLastError();
 }
 }  // namespace
@@ -231,20 +155,16 @@ long long resize_ce_workspace_floats(int B, int H, int W) {
 // extents >= 1, B C h w and B H W and the launches below 2^31, aligned non-null buffers: checked by the caller (capi.hip)
 int resize_ce_fwd_launch(const void* logit, const void* label, float* lse, float* loss, int64_t* correct, float* ws, int B, int C, int h, int w,
                          int H, int W, int ignore_index, int logit_dtype, int label_dtype, hipStream_t stream) {
-    if (logit_dtype == 0)
-        return label_dtype == 0 ? fwd_typed<float, uint8_t>(logit, label, lse, loss, correct, ws, B, C, h, w, H, W, ignore_index, stream)
-                                : fwd_typed<float, int64_t>(logit, label, lse, loss, correct, ws, B, C, h, w, H, W, ignore_index, stream);
-    return label_dtype == 0 ? fwd_typed<__bf16, uint8_t>(logit, label, lse, loss, correct, ws, B, C, h, w, H, W, ignore_index, stream)
-                            : fwd_typed<__bf16, int64_t>(logit, label, lse, loss, correct, ws, B, C, h, w, H, W, ignore_index, stream);
+    return dispatch_types(logit_dtype, label_dtype, [&](auto t, auto lt) {
+        return fwd_typed<decltype(t), decltype(lt)>(logit, label, lse, loss, correct, ws, B, C, h, w, H, W, ignore_index, stream);
+    });
 }
 
 int resize_ce_bwd_launch(const void* logit, const void* label, const float* lse, const float* grad_out, void* dlogit, int B, int C, int h, int w,
                          int H, int W, int ignore_index, int logit_dtype, int label_dtype, hipStream_t stream) {
-    if (logit_dtype == 0)
-        return label_dtype == 0 ? bwd_typed<float, uint8_t>(logit, label, lse, grad_out, dlogit, B, C, h, w, H, W, ignore_index, stream)
-                                : bwd_typed<float, int64_t>(logit, label, lse, grad_out, dlogit, B, C, h, w, H, W, ignore_index, stream);
-    return label_dtype == 0 ? bwd_typed<__bf16, uint8_t>(logit, label, lse, grad_out, dlogit, B, C, h, w, H, W, ignore_index, stream)
-                            : bwd_typed<__bf16, int64_t>(logit, label, lse, grad_out, dlogit, B, C, h, w, H, W, ignore_index, stream);
+    return dispatch_types(logit_dtype, label_dtype, [&](auto t, auto lt) {
+        return bwd_typed<decltype(t), decltype(lt)>(logit, label, lse, grad_out, dlogit, B, C, h, w, H, W, ignore_index, stream);
+    });
 }
 
 }  // namespace ppn

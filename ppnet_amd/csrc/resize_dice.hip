@@ -23,8 +23,9 @@
 //             dice_bwd_px   per pixel s(px) -> workspace (one float32 per pixel); a[b][.] and b[b][.] are derived in LDS from sums,
 //                           smooth, the class weights and the device scalar grad_out by every workgroup, and the first tile of an
 //                           image records them ([B][C][2] float64 in front of the per-pixel buffer) for the gather
-//             dice_bwd      resize_ce_bwd_kernel's gather (one writer per dlogit element, resize_ce_bwd_lanes lanes per element, a
-//                           fixed xor tree, no atomics)
+//             dice_bwd      resize_ce_bwd_kernel's gather (resize_tap.h's Gather: one writer per dlogit element, resize_ce_bwd_lanes
+//                           lanes per element, a fixed xor tree, no atomics).  Its own: the term (double)(wy wx) (p_c (g_c - s)), the
+//                           product with g in double, of EVERY pixel (the clamped label skips none), and a store without a scale
 //             a, b, g and s are combined in DOUBLE from the float32 p: where a pixel is confidently right N / Den is close to 1, a and
 //             b p nearly cancel (g and s are ~20 x smaller than a) and g - s is smaller again — in float32 that chain lost 5e-6 of a
 //             one-pixel image's gradient.  s itself is small, so its one rounding to float32 for the workspace costs 6e-8 of |s|.
@@ -42,6 +43,10 @@
 // Per-pixel arithmetic is float32 up to p (bfloat16 logits are widened on load, dlogit is rounded once on store); sums over many pixels and the backward's combination of a, b, p end in
 // double.  No kernel holds a runtime-C array: every one loops over the channels (ScratchSize 0).  Element offsets are 64-bit; the
 // caller (capi.hip) rejects C > DICE_MAX_C, B C h w, B H W and launches of 2^31 or more.  A label never indexes memory.
+//
+// What this file does as resize_ce.hip does is not copied but included (resize_tap.h): the taps, dice_fwd's softmax_sweep (it takes
+// the maximum and 1 / sum before lse is rounded, and wants no z_label), dice_loss's final_sum, dice_bwd's Gather with tap_range and
+// tap_weight, stf, and the host's dispatch_types and dispatch_lanes.  dice_fwd's per-class triple reduction is its own and stays here.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
@@ -57,12 +62,6 @@ constexpr int DICE_PER_THREAD = 4;
 constexpr int DICE_PX = DICE_THREADS * DICE_PER_THREAD;   // pixels per tile (of one image)
 constexpr int DICE_MAX_C = 256;                        // the LDS partials and coefficients are fixed arrays
 constexpr int DICE_WAVES = DICE_THREADS / 64;
-
-template <typename T>
-__device__ __forceinline__ void stf(T* p, float v) {
-    if constexpr (sizeof(T) == 4) *p = v;
-    else *p = (__bf16)v;                                                                       // rounded to nearest even, once
-}
 
 // the label clamped into [0, C - 1] (what the reference one-hot encodes), and whether it is valid (this build's rule)
 template <typename LT>
@@ -102,19 +101,12 @@ __global__ __launch_bounds__(DICE_THREADS) void dice_fwd_kernel(const T* __restr
             ty[k] = bilinear_tap(Y, h, H);
             tx[k] = bilinear_tap(X, w, W);
             const int r0 = ty[k].i0 * w, r1 = ty[k].i1 * w;
-            float m = interp(img, r0, r1, ty[k], tx[k]);
-            int arg = 0;
-            for (int c = 1; c < C; ++c) {
-                const float z = interp(img + c * plane, r0, r1, ty[k], tx[k]);
-                if (z > m) { m = z; arg = c; }                         // ties keep the lowest class
-            }
-            float s = 0.f;
-            for (int c = 0; c < C; ++c) s += expf(interp(img + c * plane, r0, r1, ty[k], tx[k]) - m);
-            mx[k] = m;
-            inv[k] = 1.f / s;
-            if (lse) lse[px0 + r] = m + logf(s);
+            const Sweep sw = softmax_sweep(img, plane, C, r0, r1, ty[k], tx[k], -1);   // no z_label wanted
+            mx[k] = sw.m;
+            inv[k] = 1.f / sw.s;
+            if (lse) lse[px0 + r] = sw.m + logf(sw.s);
             tc[k] = clamped_label(label, px0 + r, C, ignore_index, ok[k]);
-            cnt += (ok[k] && arg == tc[k]);
+            cnt += (ok[k] && sw.arg == tc[k]);
         }
     }
     // the class outside, the pixels inside: a class's three sums over the workgroup, a fixed tree
@@ -208,14 +200,8 @@ __global__ __launch_bounds__(DICE_THREADS) void dice_loss_kernel(const double* _
         a += cw ? (double)cw[c] * t : t;
     }
     for (long long i = tid; i < n_tiles; i += DICE_THREADS) n += (long long)cnt[i];
-    s_a[tid] = a;
-    s_n[tid] = n;
-    __syncthreads();
-    for (int o = DICE_THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) { s_a[tid] += s_a[tid + o]; s_n[tid] += s_n[tid + o]; }
-        __syncthreads();
-    }
-    if (tid == 0) { *loss = (float)(s_a[0] / ((double)C * (double)B)); *correct = s_n[0]; }
+    final_sum<DICE_THREADS>(a, n, s_a, s_n);
+    if (tid == 0) { *loss = (float)(a / ((double)C * (double)B)); *correct = n; }
 }
 
 // first pass of the backward: s(px) = (a[b][tc] v p_tc + sum_i b[b][i] p_i^2) / sum_i p_i, one float32 per pixel; the coefficients in LDS
@@ -267,63 +253,24 @@ __global__ __launch_bounds__(DICE_THREADS) void dice_bwd_px_kernel(const T* __re
     }
 }
 
-// resize_ce.hip's tap_range: first / last destination index in [0, n_out) whose taps touch source index y (first > last: none); the
-// scan decides membership with bilinear_tap itself, so rounding can neither drop nor double a pixel
-__device__ __forceinline__ void tap_range(int y, int n_in, int n_out, int& first, int& last) {
-    const double r = (double)n_out / (double)n_in;
-    const double lo = floor(((double)y - 0.5) * r - 0.5), hi = ceil(((double)y + 1.5) * r - 0.5);
-    const double margin = 1.0 + floor(hi * 1.0e-6);        // one, plus the float32 error of the source index (< 2.4e-7 of it)
-    const int c0 = (int)fmax(lo - margin, 0.0), c1 = (int)fmin(hi + margin, (double)(n_out - 1));
-    first = c1 + 1;
-    last = c0 - 1;
-    for (int Y = c0; Y <= c1; ++Y) {
-        const Tap t = bilinear_tap(Y, n_in, n_out);
-        if (t.i0 == y || t.i1 == y) {
-            if (first > c1) first = Y;
-            last = Y;
-        }
-    }
-}
-
-__device__ __forceinline__ float tap_weight(const Tap& t, int y) { return (t.i0 == y ? t.l0 : 0.f) + (t.i1 == y ? t.l1 : 0.f); }
-
 template <typename T, typename LT, int LANES>
 __global__ __launch_bounds__(DICE_THREADS) void dice_bwd_kernel(const T* __restrict__ logit, const LT* __restrict__ label,
                                                                  const float* __restrict__ lse, const float* __restrict__ spx,
                                                                  const double* __restrict__ coef, T* __restrict__ dlogit, long long n_out, int C,
                                                                  int h, int w, int H, int W, int ignore_index) {
-    constexpr int OUTS = DICE_THREADS / LANES;             // outputs per workgroup
-    const int lane = threadIdx.x % LANES;
-    const long long o = (long long)blockIdx.x * OUTS + threadIdx.x / LANES;
-    const bool live = o < n_out;                           // the lanes of an output agree; no early return before the shuffles
-    double acc = 0.0;                                      // a footprint of ~1000 signed terms that cancel: summed in double, rounded once
-    if (live) {
-        const int x = (int)(o % w), y = (int)((o / w) % h);
-        const int bc = (int)(o / ((long long)w * h)), b = bc / C, c = bc - b * C;
-        const double ca = coef[(size_t)bc * 2], cb = coef[(size_t)bc * 2 + 1];
-        int Y0, Y1, X0, X1;
-        tap_range(y, h, H, Y0, Y1);
-        tap_range(x, w, W, X0, X1);
-        const int ny = Y1 - Y0 + 1, nx = X1 - X0 + 1;
-        if (ny > 0 && nx > 0 && C > 1) {                  // C = 1: p is the constant 1, the gradient identically 0
-            const T* plane = logit + (size_t)bc * h * w;
-            const size_t px0 = (size_t)b * H * W;
-            const int n = ny * nx;                         // < 2^31: a subset of one image's H W pixels
-            for (int i = lane; i < n; i += LANES) {
-                const int dy = i / nx, Y = Y0 + dy, X = X0 + (i - dy * nx);
-                const size_t p = px0 + (size_t)Y * W + X;
-                bool ok;
-                const int tc = clamped_label(label, p, C, ignore_index, ok);
-                const Tap ty = bilinear_tap(Y, h, H), tx = bilinear_tap(X, w, W);
-                const double pc = (double)expf(interp(plane, ty.i0 * w, ty.i1 * w, ty, tx) - lse[p]);
-                const double g = ((ok && tc == c) ? ca : 0.0) + cb * pc;
-                acc += (double)(tap_weight(ty, y) * tap_weight(tx, x)) * (pc * (g - (double)spx[p]));
-            }
-        }
-    }
-#pragma unroll
-    for (int s = LANES / 2; s > 0; s >>= 1) acc += __shfl_xor(acc, s, LANES);
-    if (live && lane == 0) stf(dlogit + o, (float)acc);
+    const Gather<DICE_THREADS, LANES> out(n_out, C, h, w);
+    const T* plane = logit + (size_t)out.bc * h * w;
+    const double ca = out.live ? coef[(size_t)out.bc * 2] : 0.0, cb = out.live ? coef[(size_t)out.bc * 2 + 1] : 0.0;
+    // C = 1: p is the constant 1, the gradient identically 0.  No pixel is skipped: an ignored one still has p
+    const double acc = out.sum(C > 1, h, w, H, W, [&](double& sum, size_t p, int Y, int X) {
+        bool ok;
+        const int tc = clamped_label(label, p, C, ignore_index, ok);
+        const Tap ty = bilinear_tap(Y, h, H), tx = bilinear_tap(X, w, W);
+        const double pc = (double)expf(interp(plane, ty.i0 * w, ty.i1 * w, ty, tx) - lse[p]);
+        const double g = ((ok && tc == out.c) ? ca : 0.0) + cb * pc;
+        sum += (double)(tap_weight(ty, out.y) * tap_weight(tx, out.x)) * (pc * (g - (double)spx[p]));   // the product with g in double
+    });
+    if (out.live && out.lane() == 0) stf(dlogit + out.o, (float)acc);
 }
 
 __host__ inline int tiles_of(int H, int W) { return (int)(((long long)H * W + DICE_PX - 1) / DICE_PX); }
@@ -341,14 +288,6 @@ int fwd_typed(const void* logit, const void* label, const float* cw, uint32_t* w
     return (int)hipGetLastError();
 }
 
-template <typename T, typename LT, int LANES>
-void bwd_lanes(const void* logit, const void* label, const float* lse, const float* spx, const double* coef, void* dlogit, int B, int C, int h, int w,
-               int H, int W, int ignore_index, hipStream_t stream) {
-    const long long n_out = (long long)B * C * h * w, outs = DICE_THREADS / LANES;
-    hipLaunchKernelGGL((dice_bwd_kernel<T, LT, LANES>), dim3((unsigned)((n_out + outs - 1) / outs)), dim3(DICE_THREADS), 0, stream, (const T*)logit,
-                       (const LT*)label, lse, spx, coef, (T*)dlogit, n_out, C, h, w, H, W, ignore_index);
-}
-
 template <typename T, typename LT>
 int bwd_typed(const void* logit, const void* label, const float* lse, const double* sums, const float* cw, const float* grad_out, float* ws,
               void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index, float smooth, hipStream_t stream) {
@@ -357,10 +296,11 @@ int bwd_typed(const void* logit, const void* label, const float* lse, const doub
     float* spx = ws + 4 * (size_t)B * C;
     hipLaunchKernelGGL((dice_bwd_px_kernel<T, LT>), dim3((unsigned)((long long)B * tpi)), dim3(DICE_THREADS), 0, stream, (const T*)logit,
                        (const LT*)label, lse, sums, cw, grad_out, spx, coef, tpi, B, C, h, w, H, W, ignore_index, (double)smooth);
-    const int lanes = resize_ce_bwd_lanes(h, w, H, W);     // resize_ce.hip's rule: the footprint of an output is the same
-    if (lanes == 1) bwd_lanes<T, LT, 1>(logit, label, lse, spx, coef, dlogit, B, C, h, w, H, W, ignore_index, stream);
-    else if (lanes == 8) bwd_lanes<T, LT, 8>(logit, label, lse, spx, coef, dlogit, B, C, h, w, H, W, ignore_index, stream);
-    else bwd_lanes<T, LT, 64>(logit, label, lse, spx, coef, dlogit, B, C, h, w, H, W, ignore_index, stream);
+    const long long n_out = (long long)B * C * h * w;
+    dispatch_lanes(DICE_THREADS, n_out, h, w, H, W, [&](auto lanes, dim3 grid) {
+        hipLaunchKernelGGL((dice_bwd_kernel<T, LT, decltype(lanes)::value>), grid, dim3(DICE_THREADS), 0, stream, (const T*)logit, (const LT*)label,
+                           lse, spx, coef, (T*)dlogit, n_out, C, h, w, H, W, ignore_index);
+    });
     return (int)hipGetLastError();
 }
 }  // namespace
@@ -383,20 +323,20 @@ int resize_dice_fwd_launch(const void* logit, const void* label, const float* cl
                            int64_t* correct, int B, int C, int h, int w, int H, int W, int ignore_index, float smooth, int logit_dtype,
                            int label_dtype, hipStream_t stream) {
     uint32_t* ws = (uint32_t*)workspace;
-#define PPN_DICE_FWD(T, LT) fwd_typed<T, LT>(logit, label, class_weight, ws, lse, sums, loss, correct, B, C, h, w, H, W, ignore_index, smooth, stream)
-    if (logit_dtype == 0) return label_dtype == 0 ? PPN_DICE_FWD(float, uint8_t) : PPN_DICE_FWD(float, int64_t);
-    return label_dtype == 0 ? PPN_DICE_FWD(__bf16, uint8_t) : PPN_DICE_FWD(__bf16, int64_t);
-#undef PPN_DICE_FWD
+    return dispatch_types(logit_dtype, label_dtype, [&](auto t, auto lt) {
+        return fwd_typed<decltype(t), decltype(lt)>(logit, label, class_weight, ws, lse, sums, loss, correct, B, C, h, w, H, W, ignore_index, smooth,
+                                                    stream);
+    });
 }
 
 int resize_dice_bwd_launch(const void* logit, const void* label, const float* lse, const double* sums, const float* class_weight,
                            const float* grad_out, void* workspace, void* dlogit, int B, int C, int h, int w, int H, int W, int ignore_index,
                            float smooth, int logit_dtype, int label_dtype, hipStream_t stream) {
     float* ws = (float*)workspace;
-#define PPN_DICE_BWD(T, LT) bwd_typed<T, LT>(logit, label, lse, sums, class_weight, grad_out, ws, dlogit, B, C, h, w, H, W, ignore_index, smooth, stream)
-    if (logit_dtype == 0) return label_dtype == 0 ? PPN_DICE_BWD(float, uint8_t) : PPN_DICE_BWD(float, int64_t);
-    return label_dtype == 0 ? PPN_DICE_BWD(__bf16, uint8_t) : PPN_DICE_BWD(__bf16, int64_t);
-#undef PPN_DICE_BWD
+    return dispatch_types(logit_dtype, label_dtype, [&](auto t, auto lt) {
+        return bwd_typed<decltype(t), decltype(lt)>(logit, label, lse, sums, class_weight, grad_out, ws, dlogit, B, C, h, w, H, W, ignore_index,
+                                                    smooth, stream);
+    });
 }
 
 }  // namespace ppn

@@ -28,6 +28,9 @@
 // No kernel holds a runtime-C array: the sweep loops over the channels, the per-slot state is four registers (ScratchSize 0).  Element
 // offsets are 64-bit; the caller (capi.hip) rejects B C h w and B H W of 2^31 or more and C > SE_MAX_C.  A workgroup counts at most
 // ceil(tiles / groups) * SE_PX < 2^31 pixels, so an int32 bin cannot overflow.
+//
+// From resize_tap.h: the taps (Tap, bilinear_tap, ldf, interp, valid_label) and the host's dispatch_types.  The header's softmax_sweep
+// is NOT used here: this sweep starts from -inf (above) and needs neither z_label nor the exponentials.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
@@ -149,11 +152,9 @@ int seg_eval_max_classes() { return SE_MAX_C; }
 // extents >= 1, C <= SE_MAX_C, B C h w and B H W below 2^31, aligned non-null buffers: checked by the caller (capi.hip)
 int seg_eval_launch(const void* logit, const void* label, uint8_t* pred, int64_t* areas, int B, int C, int h, int w, int H, int W, int ignore_index,
                     int logit_dtype, int label_dtype, hipStream_t stream) {
-    if (logit_dtype == 0)
-        return label_dtype == 0 ? eval_typed<float, uint8_t>(logit, label, pred, areas, B, C, h, w, H, W, ignore_index, stream)
-                                : eval_typed<float, int64_t>(logit, label, pred, areas, B, C, h, w, H, W, ignore_index, stream);
-    return label_dtype == 0 ? eval_typed<__bf16, uint8_t>(logit, label, pred, areas, B, C, h, w, H, W, ignore_index, stream)
-                            : eval_typed<__bf16, int64_t>(logit, label, pred, areas, B, C, h, w, H, W, ignore_index, stream);
+    return dispatch_types(logit_dtype, label_dtype, [&](auto t, auto lt) {
+        return eval_typed<decltype(t), decltype(lt)>(logit, label, pred, areas, B, C, h, w, H, W, ignore_index, stream);
+    });
 }
 
 }  // namespace ppn

@@ -190,12 +190,13 @@ struct ConcatBwdParams {
 };
 
 namespace {
-__device__ __forceinline__ void tap_range(int r, int n_in, int n_out, int& lo, int& hi) {
+// the candidates only, in integers: the kernel tests each one itself (resize_tap.h's tap_range scans for the exact first / last member)
+__device__ __forceinline__ void candidate_range(int r, int n_in, int n_out, int& lo, int& hi) {
     const long long a = ((2LL * r - 1) * n_out - n_in) / (2LL * n_in) - 1, b = ((2LL * r + 3) * n_out - n_in) / (2LL * n_in) + 1;
     lo = (int)(a < 0 ? 0 : a);
     hi = (int)(b > n_out - 1 ? n_out - 1 : b);
 }
-__device__ __forceinline__ float tap_weight(const Tap& t, int r) { return (t.i0 == r ? t.l0 : 0.0f) + (t.i1 == r ? t.l1 : 0.0f); }
+// tap_weight: resize_tap.h
 }  // namespace
 
 template <typename T>
@@ -215,8 +216,8 @@ __global__ __launch_bounds__(256) void resize_concat_bwd_kernel(ConcatBwdParams 
         V8<T>::load(src + ((size_t)r * W0 + q) * p.Ctot, acc);
     } else {
         int i_lo, i_hi, j_lo, j_hi;
-        tap_range(r, Hl, H0, i_lo, i_hi);
-        tap_range(q, Wl, W0, j_lo, j_hi);
+        candidate_range(r, Hl, H0, i_lo, i_hi);
+        candidate_range(q, Wl, W0, j_lo, j_hi);
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = 0.0f;
         for (int i = i_lo; i <= i_hi; ++i) {

@@ -44,6 +44,7 @@ def test_header_library_bindings_and_makefile_carry_the_entry_points_at_abi_111(
     assert "resize_dice.hip" in re.search(r"^SRCS\s*:=(.*)$", mk, re.M).group(1).split()
     text = open(os.path.join(CSRC, "resize_dice.hip")).read()
     assert '#include "resize_tap.h"' in text and "bilinear_tap(int" not in text          # the shared taps: included, not copied
+    assert not re.search(r"\b(void|float)\s+(tap_range|tap_weight|stf)\s*\(", text)      # nor the gather's scan, weight and store
 
 
 def test_workspace_follows_the_header_formula():

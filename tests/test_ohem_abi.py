@@ -181,6 +181,7 @@ def test_ohem_source_cross_compiles_without_scratch_and_includes_the_shared_taps
     assert "global_atomic_add_f32" not in asm and "ds_add_f32" not in asm and "cmpswap" not in asm      # integer atomics only
     text = open(os.path.join(CSRC, "ohem_ce.hip")).read()
     assert '#include "resize_tap.h"' in text and "bilinear_tap(int" not in text and "struct Tap" not in text        # included, not copied
+    assert not re.search(r"\b(void|float)\s+(tap_range|tap_weight|stf)\s*\(", text)                   # nor the gather's scan, weight and store
 
 
 def test_ohem_cross_entropy_refuses_cpu_tensors_and_bad_options():

@@ -116,6 +116,7 @@ def test_seg_eval_source_is_built_and_uses_no_scratch(tmp_path):
     for name in ("seg_eval.hip", "resize_ce.hip"):
         text = open(os.path.join(CSRC, name)).read()
         assert '#include "resize_tap.h"' in text and "bilinear_tap(int" not in text, name     # included, not copied
+        assert not re.search(r"\b(void|float)\s+(tap_range|tap_weight|stf)\s*\(", text), name  # nor the gather's scan, weight and store
 
 
 def test_seg_eval_refuses_cpu_tensors():
