@@ -72,7 +72,8 @@ extern "C" {
  * argument list and remove nothing, which is all the version guards against.  ppn_ohem_ce_workspace, ppn_ohem_ce_fwd and
  * ppn_ohem_ce_bwd joined at 111 in the same way, and so did ppn_resize_dice_workspace, ppn_resize_dice_fwd and ppn_resize_dice_bwd, and
  * ppn_upsample2x_nhwc_bwd, ppn_upsample2x_concat_nhwc_bwd and ppn_resize_concat_nhwc_bwd, and ppn_residual_layernorm_train_fwd,
- * ppn_residual_layernorm_bwd_workspace and ppn_residual_layernorm_bwd. */
+ * ppn_residual_layernorm_bwd_workspace and ppn_residual_layernorm_bwd, and ppn_patch_merge_ln_fwd, ppn_patch_merge_ln_bwd_workspace,
+ * ppn_patch_merge_ln_bwd, ppn_patch_merge_ln_rows and ppn_patch_merge_ln_max_blocks. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -551,6 +552,36 @@ int ppn_residual_layernorm_train_fwd(const void* x, const void* a, const void* g
 int ppn_residual_layernorm_bwd(const void* gy, const void* gx, const void* xn, const void* a, const void* gamma, const float* scale,
                                const void* w, const float* stats, void* dx, void* da, void* dgamma, void* dw, void* dbeta, float* workspace,
                                int64_t workspace_floats, int64_t rows, int64_t rows_per_image, int32_t C, int32_t dtype, void* stream);
+
+/* DiNAT_s's PatchMerging in front of its reduction GEMM (csrc/patch_merge_ln.hip; reference SegNet/dinats.py:74-104): the 2 x 2 gather
+ * of a token grid fused with the LayerNorm over the gathered 4C values, forward and backward.
+ *
+ * x [B][H][W][C] contiguous NHWC of `dtype` (0 = float32, 1 = bfloat16); Ho = ceil(H / 2), Wo = ceil(W / 2), rows = B Ho Wo.
+ * ppn_patch_merge_ln_fwd: row (b, i, j) of y [B][Ho][Wo][4C] is LayerNorm_{4C}(concat_q x[b, 2i + (q & 1), 2j + (q >> 1), :], q = 0..3)
+ *   with biased variance and `eps`, scaled by gamma and shifted by beta (each [4C] of `dtype`), rounded once.  A token outside the grid
+ *   (odd H or W) reads as zeros and enters the statistics as zeros.  Statistics are float32, mean first and then the centred squares.
+ *   stats [rows][2] float32 receives (mean, rstd) of every row; NULL = not wanted (inference).
+ * ppn_patch_merge_ln_bwd: with xhat = (row - mean) rstd and g = gy gamma, quadrant q of rstd (g - mean(g) - xhat mean(g xhat)) is stored
+ *   to dx[b, 2i + (q & 1), 2j + (q >> 1), :] (every element of dx [B][H][W][C] is written exactly once; the gradient of a padded position
+ *   is dropped), dgamma = sum_rows gy xhat and dbeta = sum_rows gy ([4C] of `dtype`; NULL = not wanted) are summed in float32 without
+ *   atomics — one [2][4C] partial per workgroup in `workspace`, added in a fixed order by a second kernel — and rounded once: two calls
+ *   give the same bits.  gy [B][Ho][Wo][4C] of `dtype`; x, stats and gamma as in the forward.
+ * ppn_patch_merge_ln_bwd_workspace(B, H, W, C): the bytes `workspace` holds,
+ *   4 * min(ceil(rows / ppn_patch_merge_ln_rows(C)), ppn_patch_merge_ln_max_blocks()) * 2 * 4C; < 0 for sizes the entry points refuse.
+ * ppn_patch_merge_ln_rows(C): the rows of one workgroup tile, 256 / (C / 8); 0 for a width outside the set.
+ * ppn_patch_merge_ln_max_blocks(): the most workgroups of a launch; past that many tiles a workgroup strides over several.
+ *
+ * C in {8, 16, 32, 64, 128, 256, 512}.  Before any HIP call: PPN_E_INVALID for a NULL required pointer, a tensor pointer that is not
+ * 16-byte aligned (stats: 4), an extent below 1, a dtype outside {0, 1}, an eps that is negative or not finite, 2^31 elements and more
+ * in x or in the gathered rows; PPN_E_UNSUPPORTED for another width. */
+int     ppn_patch_merge_ln_rows(int C);
+int     ppn_patch_merge_ln_max_blocks(void);
+int     ppn_patch_merge_ln_fwd(const void* x, const void* gamma, const void* beta, void* y, float* stats /* may be NULL */,
+                               int B, int H, int W, int C, float eps, int dtype, void* stream);
+int64_t ppn_patch_merge_ln_bwd_workspace(int B, int H, int W, int C);   /* bytes; < 0 for invalid sizes */
+int     ppn_patch_merge_ln_bwd(const void* gy, const void* x, const float* stats, const void* gamma, void* workspace,
+                               void* dx, void* dgamma /* may be NULL */, void* dbeta /* may be NULL */,
+                               int B, int H, int W, int C, int dtype, void* stream);
 
 /* Bilinear x2 up-sampling of an NHWC tensor x [B][H][W][C] -> y [B][2H][2W][C] with PyTorch's
  * F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) arithmetic (the SETR-UP head's Upsample,

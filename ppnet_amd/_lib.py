@@ -61,7 +61,9 @@ EXPORTS = ("ppn_version", "ppn_error_string", "ppn_last_hip_error", "ppn_polyfit
            "ppn_ohem_ce_workspace", "ppn_ohem_ce_fwd", "ppn_ohem_ce_bwd",
            "ppn_resize_dice_workspace", "ppn_resize_dice_fwd", "ppn_resize_dice_bwd",
            "ppn_upsample2x_nhwc_bwd", "ppn_upsample2x_concat_nhwc_bwd", "ppn_resize_concat_nhwc_bwd",
-           "ppn_residual_layernorm_train_fwd", "ppn_residual_layernorm_bwd_workspace", "ppn_residual_layernorm_bwd")
+           "ppn_residual_layernorm_train_fwd", "ppn_residual_layernorm_bwd_workspace", "ppn_residual_layernorm_bwd",
+           "ppn_patch_merge_ln_fwd", "ppn_patch_merge_ln_bwd_workspace", "ppn_patch_merge_ln_bwd", "ppn_patch_merge_ln_rows",
+           "ppn_patch_merge_ln_max_blocks")
 
 
 def _load():
@@ -143,6 +145,12 @@ def _load():
     lib.ppn_residual_layernorm_bwd_workspace.argtypes = [C.c_int64, C.c_int32]
     lib.ppn_residual_layernorm_bwd_workspace.restype = C.c_int64
     lib.ppn_residual_layernorm_bwd.argtypes = [_p] * 14 + [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _p]
+    lib.ppn_patch_merge_ln_fwd.argtypes = [_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_int, _p]
+    lib.ppn_patch_merge_ln_bwd_workspace.argtypes = [C.c_int] * 4
+    lib.ppn_patch_merge_ln_bwd_workspace.restype = C.c_int64
+    lib.ppn_patch_merge_ln_bwd.argtypes = [_p] * 8 + [C.c_int] * 5 + [_p]
+    lib.ppn_patch_merge_ln_rows.argtypes = [C.c_int]
+    lib.ppn_patch_merge_ln_max_blocks.argtypes = []
     lib.ppn_grid_to_image.argtypes = [_p, _p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, _p]
     lib.ppn_seg_labels_2class.argtypes = [_p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
     lib.ppn_bias_act_nhwc.argtypes = [_p, _p, C.c_int64, C.c_int32, C.c_float, C.c_int32, _p]
@@ -192,7 +200,8 @@ def _load():
     for name in EXPORTS:
         getattr(lib, name)
         if name not in ("ppn_error_string", "ppn_na2d_bwd_workspace", "ppn_na2d_bwd_vpad_workspace", "ppn_mhsa_bwd_workspace", "ppn_swin_wmsa_bwd_workspace",
-                        "ppn_resize_ce_workspace", "ppn_ohem_ce_workspace", "ppn_resize_dice_workspace", "ppn_residual_layernorm_bwd_workspace"):
+                        "ppn_resize_ce_workspace", "ppn_ohem_ce_workspace", "ppn_resize_dice_workspace", "ppn_residual_layernorm_bwd_workspace",
+                        "ppn_patch_merge_ln_bwd_workspace"):
             getattr(lib, name).restype = C.c_int
     return lib
 

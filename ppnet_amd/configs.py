@@ -94,3 +94,24 @@ VIT_BASE_SETRUP = dict(
         in_channels=768, channels=512, in_index=-1, num_classes=2, norm_cfg=dict(type="SyncBN", requires_grad=True), align_corners=False,
         loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0)),
     train_cfg=dict(), test_cfg=dict(mode="whole"))
+
+# DiNAT_s-B + SETR-UP: configs/dinats/dinats_base.py:1-22 names '../_base_/models/dinats.py' (line 2), which the reference tree lacks,
+# so this is a RECONSTRUCTION, as VIT_BASE_SETRUP is.  Backbone: the constructor defaults of the class itself (SegNet/dinats.py:207-228:
+# patch 4, mlp_ratio 4, qkv_bias, patch_norm, out_indices 0-3, no frozen stage) with dinats_base.py's overrides (lines 6-17).  Head: the
+# config's decode-head overrides (lines 18-22: in_channels 1024, num_convs 4, up_scale 2, num_classes 2) are exactly dinat_base.py's
+# (configs/dinat/dinat_base.py:20-24), so the SETR-UP head they override is taken to be that config's base,
+# _base_/models/dinat.py:23-43.  `pretrained` (an ImageNet checkpoint path on the authors' machine, dinats_base.py:14) is left out: load
+# one with DiNAT_s.init_weights.  The config trains with AdamW (lines 25-29): train.segnet_adamw.
+DINATS_BASE_SETRUP = dict(
+    type="EncoderDecoder", pretrained=None,
+    backbone=dict(   # dinats.py:207-228 with dinats_base.py:6-17
+        type="DiNAT_s", pretrain_img_size=224, patch_size=4, in_chans=3, embed_dim=128, depths=[2, 2, 18, 2], num_heads=[4, 8, 16, 32],
+        kernel_size=7, dilations=[[1, 16], [1, 8], [1, 2, 1, 3, 1, 4, 1, 2, 1, 3, 1, 4, 1, 2, 1, 3, 1, 4], [1, 2]], mlp_ratio=4.0,
+        qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.3, patch_norm=True, out_indices=(0, 1, 2, 3),
+        frozen_stages=-1),
+    decode_head=dict(   # _base_/models/dinat.py:23-43 with dinats_base.py:18-22
+        type="SETRUPHead", norm_layer=dict(type="LN", eps=1e-6, requires_grad=True), num_convs=4, up_scale=2, kernel_size=3,
+        init_cfg=[dict(type="Constant", val=1.0, bias=0, layer="LayerNorm"), dict(type="Normal", std=0.01, override=dict(name="conv_seg"))],
+        in_channels=1024, channels=512, in_index=-1, num_classes=2, norm_cfg=dict(type="SyncBN", requires_grad=True), align_corners=False,
+        loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0)),
+    train_cfg=dict(), test_cfg=dict(mode="whole"))

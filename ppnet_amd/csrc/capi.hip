@@ -701,6 +701,54 @@ int ppn_residual_layernorm_bwd(const void* gy, const void* gx, const void* xn, c
     return PPN_OK;
 }
 
+int ppn_patch_merge_ln_rows(int C) { return ppn::patch_merge_ln_rows(C); }
+int ppn_patch_merge_ln_max_blocks(void) { return ppn::patch_merge_ln_max_blocks(); }
+
+// what the three patch-merge entry points check alike: extents, width, element counts.  PPN_OK, PPN_E_INVALID or PPN_E_UNSUPPORTED
+static int patch_merge_sizes(int B, int H, int W, int C) {
+    if (B < 1 || H < 1 || W < 1 || C < 1) return PPN_E_INVALID;
+    if (ppn::patch_merge_ln_rows(C) == 0) return PPN_E_UNSUPPORTED;            // C outside {8, 16, 32, 64, 128, 256, 512}
+    const long long Ho = ((long long)H + 1) / 2, Wo = ((long long)W + 1) / 2;
+    // x and the gathered rows (the padded grid: a little more than x at odd sizes) stay below 2^31 elements; overflow-safe in this order
+    if ((long long)B * H >= 0x7fffffffLL || (long long)B * H * W >= 0x7fffffffLL || (long long)B * H * W * C >= 0x7fffffffLL) return PPN_E_INVALID;
+    if (B * Ho * Wo * 4 * C >= 0x7fffffffLL) return PPN_E_INVALID;
+    return PPN_OK;
+}
+
+int64_t ppn_patch_merge_ln_bwd_workspace(int B, int H, int W, int C) {
+    if (patch_merge_sizes(B, H, W, C) != PPN_OK) return -1;
+    return ppn::patch_merge_ln_bwd_workspace_bytes((long long)B * ((H + 1) / 2) * ((W + 1) / 2), C);
+}
+
+int ppn_patch_merge_ln_fwd(const void* x, const void* gamma, const void* beta, void* y, float* stats, int B, int H, int W, int C, float eps,
+                           int dtype, void* stream) {
+    if (!x || !gamma || !beta || !y) return PPN_E_INVALID;                                               // stats may be NULL: inference
+    if ((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y) & 15) != 0 || ((uintptr_t)stats & 3) != 0) return PPN_E_INVALID;
+    if (dtype != 0 && dtype != 1) return PPN_E_INVALID;
+    if (!(eps >= 0.0f) || eps > 3.0e38f) return PPN_E_INVALID;                                           // NaN, negative, inf
+    const int ok = patch_merge_sizes(B, H, W, C);
+    if (ok != PPN_OK) return ok;
+    const int e = ppn::patch_merge_ln_fwd_launch(x, gamma, beta, y, stats, B, H, W, C, eps, dtype, (hipStream_t)stream);
+    if (e == -1) return PPN_E_UNSUPPORTED;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_patch_merge_ln_bwd(const void* gy, const void* x, const float* stats, const void* gamma, void* workspace, void* dx, void* dgamma,
+                           void* dbeta, int B, int H, int W, int C, int dtype, void* stream) {
+    if (!gy || !x || !stats || !gamma || !workspace || !dx) return PPN_E_INVALID;                        // dgamma, dbeta may be NULL: not wanted
+    if ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gamma | (uintptr_t)workspace | (uintptr_t)dx | (uintptr_t)dgamma | (uintptr_t)dbeta) & 15) != 0 ||
+        ((uintptr_t)stats & 3) != 0)
+        return PPN_E_INVALID;
+    if (dtype != 0 && dtype != 1) return PPN_E_INVALID;
+    const int ok = patch_merge_sizes(B, H, W, C);
+    if (ok != PPN_OK) return ok;
+    const int e = ppn::patch_merge_ln_bwd_launch(gy, x, stats, gamma, (float*)workspace, dx, dgamma, dbeta, B, H, W, C, dtype, (hipStream_t)stream);
+    if (e == -1) return PPN_E_UNSUPPORTED;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_upsample2x_nhwc(const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t relu, int32_t dtype,
                         void* stream) {
     return ppn_upsample2x_nhwc_bias(x, nullptr, y, B, H, W, C, relu, dtype, stream);

@@ -133,6 +133,16 @@ int residual_ln_bwd_launch(const void* gy, const void* gx, const void* xn, const
                            const void* w, void* dx, void* da, void* dgamma, void* dw, void* dbeta, float* workspace, long long rows,
                            long long rows_per_image, int C, int dtype, hipStream_t stream);
 
+// patch_merge_ln.hip: DiNAT_s's 2 x 2 patch gather fused with the LayerNorm over 4C, forward and backward; rows per workgroup tile
+// (0 = a width the kernels do not take), the workgroup cap, the backward's workspace in bytes (-1 = not taken).  Launches: -1 = width
+int patch_merge_ln_rows(int C);
+int patch_merge_ln_max_blocks();
+long long patch_merge_ln_bwd_workspace_bytes(long long rows, int C);
+int patch_merge_ln_fwd_launch(const void* x, const void* gamma, const void* beta, void* y, float* stats, int B, int H, int W, int C, float eps,
+                              int dtype, hipStream_t stream);
+int patch_merge_ln_bwd_launch(const void* gy, const void* x, const float* stats, const void* gamma, float* workspace, void* dx, void* dgamma,
+                              void* dbeta, int B, int H, int W, int C, int dtype, hipStream_t stream);
+
 int resize_concat_launch(const void* const* x, const int* hw, const int* ch, int n, void* out, int B, int dtype, hipStream_t stream);
 int adaptive_pools_launch(const void* x, void* const* y, const int* scales, int n, int B, int H, int W, int C, int dtype, hipStream_t stream);
 int upsample2x_launch(const void* x, const void* bias, const void* add, void* y, int B, int H, int W, int C, int relu, int dtype, hipStream_t stream);

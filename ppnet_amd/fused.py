@@ -1420,3 +1420,116 @@ def resize_dice(logit, labels, ignore_index=255, smooth=1.0, class_weight=None):
         return _ResizeDiceFunction.apply(logit, labels, cw, int(ignore_index), smooth)
     loss, correct, _, _ = _resize_dice_fwd(logit.detach(), labels, cw, int(ignore_index), smooth, False)
     return loss, correct
+
+
+# ---------------------------------------------------------------------------------------------------------------- DiNAT_s patch merge
+MERGE_CALLS = {"fwd": 0, "bwd": 0}       # launches of ppn_patch_merge_ln_fwd / ppn_patch_merge_ln_bwd (like NORM_CALLS)
+MERGE_WIDTHS = frozenset(8 << i for i in range(7))                         # csrc/patch_merge_ln.hip: C / 8 lanes per row, a power of two up to 64
+MERGE_MAX_BLOCKS = 1024                  # workgroups at most (ppn_patch_merge_ln_max_blocks): beyond that many tiles a workgroup strides
+
+
+def patch_merge_rows(C):
+    """Rows of one workgroup tile of csrc/patch_merge_ln.hip (ppn_patch_merge_ln_rows): 256 / (C / 8); 0 for a width it does not take."""
+    return 256 // (C // 8) if C in MERGE_WIDTHS else 0
+
+
+def patch_merge_workspace_bytes(B, H, W, C):
+    """ppn_patch_merge_ln_bwd_workspace's formula (include/ppnet_hip.h): one [2][4C] float32 partial per workgroup."""
+    rows = B * -(-H // 2) * -(-W // 2)
+    return 4 * min(-(-rows // patch_merge_rows(C)), MERGE_MAX_BLOCKS) * 2 * 4 * C
+
+
+def library_merge():
+    """PPNET_LIBRARY_MERGE=1 (read at call time, like PPNET_LIBRARY_NORM): patch_merge_ln takes the torch composition (pad, four strided
+    slices, cat, F.layer_norm and the framework's backwards) instead of the HIP pair, with and without autograd."""
+    return bool(os.environ.get("PPNET_LIBRARY_MERGE"))
+
+
+def patch_merge_ln_ok(x, ln):
+    """Whether patch_merge_ln runs x [B,H,W,C] on the HIP pair: a CUDA tensor of float32 / bfloat16, a width of MERGE_WIDTHS, an affine
+    LayerNorm over 4C whose parameters live on x's device in float32 or bfloat16 (a bfloat16 autocast step keeps float32 parameters:
+    patch_merge_ln runs the wider dtype), fewer than 2^31 elements, and the knob off.  Everything else is the torch composition."""
+    if library_merge() or not x.is_cuda or x.dtype not in _DT or x.dim() != 4 or x.numel() == 0 or x.shape[-1] not in MERGE_WIDTHS:
+        return False
+    B, H, W, C = x.shape
+    if tuple(ln.normalized_shape) != (4 * C,) or ln.weight is None or ln.bias is None:
+        return False
+    if any(t.dtype not in _DT or t.device != x.device for t in (ln.weight, ln.bias)):
+        return False
+    return B * -(-H // 2) * -(-W // 2) * 4 * C < 2 ** 31 - 1
+
+
+def patch_merge_gather(x):
+    """The reference's gather (SegNet/dinats.py:88-99): zero-pad to even sizes, x0 (even row, even col) | x1 (odd row, even col) |
+    x2 (even row, odd col) | x3 (odd row, odd col) -> [B,ceil(H/2),ceil(W/2),4C]."""
+    H, W = x.shape[1], x.shape[2]
+    if H % 2 or W % 2:
+        x = F.pad(x, (0, 0, 0, W % 2, 0, H % 2))
+    return torch.cat([x[:, 0::2, 0::2, :], x[:, 1::2, 0::2, :], x[:, 0::2, 1::2, :], x[:, 1::2, 1::2, :]], -1)
+
+
+def _patch_merge_ln_torch(x, ln):
+    return F.layer_norm(patch_merge_gather(x), ln.normalized_shape, ln.weight, ln.bias, ln.eps)
+
+
+def _pm_fwd(x, w, b, eps, want_stats):
+    """ppn_patch_merge_ln_fwd on contiguous tensors of one dtype: (y [B,Ho,Wo,4C], stats [rows,2] float32 or None)."""
+    B, H, W, C = x.shape
+    Ho, Wo = -(-H // 2), -(-W // 2)
+    y = torch.empty(B, Ho, Wo, 4 * C, dtype=x.dtype, device=x.device)
+    stats = torch.empty(B * Ho * Wo, 2, dtype=torch.float32, device=x.device) if want_stats else None
+    with torch.cuda.device(x.device):
+        rc = L.lib.ppn_patch_merge_ln_fwd(_p(x), _p(w), _p(b), _p(y), _p(stats), B, H, W, C, float(eps), _DT[x.dtype], _stream(x))
+    L.check(rc, "ppn_patch_merge_ln_fwd")
+    MERGE_CALLS["fwd"] += 1
+    return y, stats
+
+
+def _pm_bwd(gy, x, stats, w, want_params):
+    """ppn_patch_merge_ln_bwd on contiguous tensors: (dx, dgamma, dbeta), the last two None where not wanted."""
+    B, H, W, C = x.shape
+    dx = torch.empty_like(x)
+    dgamma, dbeta = (torch.empty_like(w), torch.empty_like(w)) if want_params else (None, None)
+    need = L.lib.ppn_patch_merge_ln_bwd_workspace(B, H, W, C)
+    ws = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = L.lib.ppn_patch_merge_ln_bwd(_p(gy), _p(x), _p(stats), _p(w), _p(ws), _p(dx), _p(dgamma), _p(dbeta), B, H, W, C, _DT[x.dtype],
+                                          _stream(x))
+    L.check(rc, "ppn_patch_merge_ln_bwd")
+    MERGE_CALLS["bwd"] += 1
+    return dx, dgamma, dbeta
+
+
+class _PatchMergeLNFunction(torch.autograd.Function):
+    """y = LayerNorm_{4C}(2 x 2 gather of x) on ppn_patch_merge_ln_fwd / ppn_patch_merge_ln_bwd; x, gamma and beta of one dtype.  Saved: x,
+    the row statistics [rows,2] and gamma — no [.., 4C] tensor."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, eps):
+        x, w, b = x.contiguous(), w.detach().contiguous(), b.detach().contiguous()
+        y, stats = _pm_fwd(x, w, b, eps, True)
+        ctx.save_for_backward(x, stats, w)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, stats, w = ctx.saved_tensors
+        need_x, need_w, need_b, _ = ctx.needs_input_grad
+        dx, dgamma, dbeta = _pm_bwd(gy.to(x.dtype).contiguous(), x, stats, w, need_w or need_b)
+        return dx if need_x else None, dgamma if need_w else None, dbeta if need_b else None, None
+
+
+def patch_merge_ln(x, ln):
+    """ln(2 x 2 gather of x) for x [B,H,W,C] and a LayerNorm over 4C -> [B,ceil(H/2),ceil(W/2),4C]: DiNAT_s's PatchMerging in front of its
+    reduction (SegNet/dinats.py:88-102).  On the GPU one kernel reads x once and writes y once (ppn_patch_merge_ln_fwd with stats = NULL);
+    while autograd records, the training pair (_PatchMergeLNFunction).  No size gate: the pair replaces about six framework ops each way
+    (tools/patch_merge_timing.py).  Tokens and parameters of two dtypes — bfloat16 tokens in front of float32
+    parameters, the later levels of a bfloat16 autocast step — run in the wider one and y has it, as autocast runs a LayerNorm in
+    float32.  CPU tensors, other dtypes, widths outside MERGE_WIDTHS and PPNET_LIBRARY_MERGE=1 take the torch composition."""
+    if not patch_merge_ln_ok(x, ln):
+        return _patch_merge_ln_torch(x, ln)
+    dt = torch.promote_types(x.dtype, torch.promote_types(ln.weight.dtype, ln.bias.dtype))
+    if recording(x, ln.weight, ln.bias):
+        return _PatchMergeLNFunction.apply(x.to(dt), ln.weight.to(dt), ln.bias.to(dt), ln.eps)
+    return _pm_fwd(x.to(dt).contiguous(), ln.weight.detach().to(dt).contiguous(), ln.bias.detach().to(dt).contiguous(), ln.eps, False)[0]

@@ -1,7 +1,7 @@
-"""SegNet = a backbone (NAT / DiNAT, Swin, ViT) + a decode head (SETR-UP, UPerNet, UPerPUP; FCN auxiliary) wired as the reference's
+"""SegNet = a backbone (NAT / DiNAT, DiNAT_s, Swin, ViT) + a decode head (SETR-UP, UPerNet, UPerPUP; FCN auxiliary) wired as the reference's
 EncoderDecoder (mmseg/models/segmentors/encoder_decoder.py:63-80,200-265) — plain nn.Modules with the reference's constructor
 arguments and checkpoint key names (`backbone.*`, `decode_head.*`, `auxiliary_head.*`), so mmcv `{'state_dict', 'meta'}`
-checkpoints load.  The parts live in dense.py (dispatch policy), nat.py / swin.py / vit.py, heads.py and configs.py, none of which
+checkpoints load.  The parts live in dense.py (dispatch policy), nat.py / dinats.py / swin.py / vit.py, heads.py and configs.py, none of which
 imports this module; every name it defined while it held them all is re-exported below under its earlier spelling (same objects)."""
 import os
 
@@ -10,7 +10,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import fused
-from .configs import (DINAT_BASE, NAT_BASE_UPER, NAT_BASE_UPERPUP, SWIN_BASE_SETRUP, SWIN_BASE_UPER, SWIN_BASE_UPERPUP,  # noqa: F401
+from .configs import (DINAT_BASE, DINATS_BASE_SETRUP, NAT_BASE_UPER, NAT_BASE_UPERPUP, SWIN_BASE_SETRUP, SWIN_BASE_UPER, SWIN_BASE_UPERPUP,  # noqa: F401
                       VIT_BASE_SETRUP, _SWIN_BASE_BACKBONE, _SWIN_NORM_CFG, _UPERPUP_AUX)
 from .dense import (IMG_MEAN, IMG_STD, LIBRARY_GEMM_BELOW_C, LIBRARY_GEMM_FROM_C, drop_path, normalize_images)  # noqa: F401
 from .dense import accumulate as _accumulate, bias32 as _bias32, library_width as _library_width, linear as _linear  # noqa: F401
@@ -18,6 +18,7 @@ from .dense import mfma_weights as _mfma_weights, own_gemm_ok as _own_gemm_ok, u
 from .heads import (FCNHead, SETRUPHead, UPerHead, UPerPUPHead, _ConvModule, _Upsample, decode_losses, dice_loss,  # noqa: F401
                     resized_decode_losses, resized_head_losses)
 from .heads import OHEMPixelSampler, eval_areas, ohem_weight, resized_eval_areas  # noqa: F401
+from .dinats import DiNAT_s
 from .na import NeighborhoodAttention2D  # noqa: F401
 from .nat import NAT, ConvDownsampler, ConvTokenizer, DiNAT, Mlp, NATBlock, NATLayer, _fold_doc  # noqa: F401
 from .swin import SwinTransformer
@@ -36,7 +37,7 @@ class SegNet(nn.Module):
         bb_type = bb_cfg.pop("type", "DiNAT")
         if pretrained is not None and bb_cfg.get("pretrained") is None:
             bb_cfg["pretrained"] = pretrained                                  # encoder_decoder.py:32-36
-        self.backbone = {"NAT": NAT, "DiNAT": DiNAT, "SwinTransformer": SwinTransformer,
+        self.backbone = {"NAT": NAT, "DiNAT": DiNAT, "DiNAT_s": DiNAT_s, "SwinTransformer": SwinTransformer,
                          "VisionTransformer": VisionTransformer}[bb_type](**bb_cfg)
         head_cfg = dict(decode_head or DINAT_BASE["decode_head"])
         head_type = head_cfg.pop("type", "SETRUPHead")

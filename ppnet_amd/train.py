@@ -63,6 +63,22 @@ def segnet_optimizer(model, lr=0.08, momentum=0.9, weight_decay=0.0, head_lr_mul
     return torch.optim.SGD([g for g in groups if g["params"]], lr=lr, momentum=momentum, weight_decay=weight_decay)
 
 
+def segnet_adamw(model, lr=6e-5, betas=(0.9, 0.999), weight_decay=0.01, no_decay=("rpb", "norm")):
+    """AdamW with the parameter groups of SegNet/configs/dinats/dinats_base.py:25-29 (paramwise_cfg custom_keys {'rpb': decay_mult 0,
+    'norm': decay_mult 0}): a parameter whose full name CONTAINS one of the keys gets weight decay 0, every other one `weight_decay`.
+    That is mmcv's DefaultOptimizerConstructor rule for custom_keys — a substring match on the parameter's name — written from its
+    documentation: mmcv's source is not part of the reference tree.  Every trainable parameter lands in exactly one group; the groups
+    carry `base_lr` for segnet_set_lr (the config's schedule is the same warm-up poly one).  The config's Fp16OptimizerHook is not
+    built: a bfloat16 autocast step is this build's mixed precision."""
+    decay, plain = [], []
+    for name, p in model.named_parameters():
+        if p.requires_grad:
+            (plain if any(k in name for k in no_decay) else decay).append(p)
+    groups = [{"params": decay, "lr": lr, "base_lr": lr, "weight_decay": weight_decay},
+              {"params": plain, "lr": lr, "base_lr": lr, "weight_decay": 0.0}]
+    return torch.optim.AdamW([g for g in groups if g["params"]], lr=lr, betas=tuple(float(b) for b in betas), weight_decay=weight_decay)
+
+
 def segnet_set_lr(optimizer, it, max_iters, **schedule):
     for g in optimizer.param_groups:
         g["lr"] = mmseg_poly_lr(g.get("base_lr", g["lr"]), it, max_iters, **schedule)
