@@ -73,7 +73,7 @@ extern "C" {
  * ppn_ohem_ce_bwd joined at 111 in the same way, and so did ppn_resize_dice_workspace, ppn_resize_dice_fwd and ppn_resize_dice_bwd, and
  * ppn_upsample2x_nhwc_bwd, ppn_upsample2x_concat_nhwc_bwd and ppn_resize_concat_nhwc_bwd, and ppn_residual_layernorm_train_fwd,
  * ppn_residual_layernorm_bwd_workspace and ppn_residual_layernorm_bwd, and ppn_patch_merge_ln_fwd, ppn_patch_merge_ln_bwd_workspace,
- * ppn_patch_merge_ln_bwd, ppn_patch_merge_ln_rows and ppn_patch_merge_ln_max_blocks. */
+ * ppn_patch_merge_ln_bwd, ppn_patch_merge_ln_rows and ppn_patch_merge_ln_max_blocks, and ppn_seg_tta. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -396,6 +396,38 @@ int ppn_seg_eval(const void* logit /* [B][C][h][w] f32 | bf16 */, const void* la
                  uint8_t* pred /* [B][H][W], may be NULL */, int64_t* areas /* [3][C]: intersect | pred | label */,
                  int B, int C, int h, int w, int H, int W, int ignore_index,
                  int logit_dtype /* 0 f32, 1 bf16 */, int label_dtype /* 0 u8, 1 i64 */, void* stream);
+
+/* The merge of a multi-scale + flip test-time augmentation (mmseg's aug_test, encoder_decoder.py:200-285: per augmentation resize to
+ * the augmentation's image size, resize to ori_shape, softmax, flip back, add; then / len(imgs) and argmax) in ONE launch, from the
+ * heads' LOW-resolution logits of up to PPN_SEG_TTA_MAX_AUGS augmentations to labels.  For output pixel (Y, X) and augmentation a:
+ * the source pixel (Ys, Xs) is (Y, X), (Y, W-1-X) for flip 1 (horizontal) or (H-1-Y, X) for flip 2 (vertical); the logit of a class
+ * is the two bilinear resizes (h,w) -> (hm,wm) -> (H,W) composed, both align_corners=False with ppn_resize_ce_fwd's own tap arithmetic
+ * (torch's float32 rule, one shared inline function): stage 2's taps of Ys in hm / Xs in wm name up to 2 x 2 mid-grid positions, each
+ * a stage-1 interpolation on the (h,w) plane (at most 4 x 4 loads per class), combined in the same order; softmax = maximum,
+ * expf(z - m), 1 / s; the probabilities are summed over the augmentations in index order and divided by (float)n_augs.  pred [B][H][W]
+ * uint8, when not NULL, is the argmax of that mean, WRITTEN for every pixel at any alignment (four pixels per store where the address
+ * allows): ties go to the lowest class, a NaN never wins and all NaN is class 0 (ppn_seg_eval's rule; a NaN logit makes every
+ * probability of its pixel NaN).  prob [B][C][H][W] float32, when not NULL, receives the mean probabilities.  float32 throughout for
+ * both logit dtypes (0 = float32, 1 = bfloat16: widened on load, nothing is rounded to bfloat16 in between — the library composition
+ * rounds every tensor it materialises).  With one augmentation, hm = H, wm = W, flip 0 and finite logits stage 2 is 1 z + 0 z' and
+ * pred is ppn_seg_eval's pred bit for bit.  C <= PPN_SEG_TTA_REG_CLASSES: the per-class sums are registers and prob may be NULL;
+ * larger C, up to 256: prob is required and is the accumulator (one work-item owns its pixels for every augmentation: no atomics, no
+ * race, no zeroing by the caller).  Every result is bitwise reproducible.  augs is a HOST array, copied into a by-value kernel
+ * argument: no device allocation and no synchronisation in the call; each augmentation has its own (h, w), all share B, C and the
+ * dtype.  NULL augs, n_augs outside [1, PPN_SEG_TTA_MAX_AUGS], a NULL or not 16-byte aligned logit, an extent <= 0, a flip outside
+ * {0, 1, 2}, C > 256, C > PPN_SEG_TTA_REG_CLASSES with NULL prob, pred and prob both NULL, B C h w, B C H W or B H W >= 2^31 and a
+ * dtype other than 0 / 1 return PPN_E_INVALID before any HIP call. */
+#define PPN_SEG_TTA_MAX_AUGS    16
+#define PPN_SEG_TTA_REG_CLASSES 8
+typedef struct ppn_tta_aug {
+    const void* logit;          /* [B][C][h][w] f32 | bf16, device                                            */
+    int32_t     h, w;           /* the head's resolution for this augmentation                                */
+    int32_t     hm, wm;         /* the augmentation's image size (encode_decode's resize target)              */
+    int32_t     flip;           /* 0 none, 1 horizontal, 2 vertical                                           */
+} ppn_tta_aug;
+int ppn_seg_tta(const ppn_tta_aug* augs /* HOST array */, int n_augs, uint8_t* pred /* [B][H][W], may be NULL */,
+                float* prob /* [B][C][H][W], may be NULL when C <= PPN_SEG_TTA_REG_CLASSES */,
+                int B, int C, int H, int W, int logit_dtype /* 0 f32, 1 bf16 */, void* stream);
 
 /* ppn_resize_ce_fwd / _bwd with mmseg's OHEMPixelSampler (core/seg/sampler/ohem_pixel_sampler.py:32-85) and CrossEntropyLoss's
  * class_weight (losses/cross_entropy_loss.py:10-33): the same bilinear resize of logit [B][C][h][w] to H x W (the same tap

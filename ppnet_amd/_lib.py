@@ -47,7 +47,12 @@ class MapsStruct(C.Structure):
         "n_obstacles", "flags", "records")]
 
 
-ABI_VERSION = 111          # include/ppnet_hip.h: PPN_ABI_VERSION (tests/test_capi_exports.py keeps the two equal)
+class TtaAug(C.Structure):
+    """ppn_tta_aug"""
+    _fields_ = [("logit", _p), ("h", C.c_int32), ("w", C.c_int32), ("hm", C.c_int32), ("wm", C.c_int32), ("flip", C.c_int32)]
+
+
+ABI_VERSION = 111         # include/ppnet_hip.h: PPN_ABI_VERSION (tests/test_capi_exports.py keeps the two equal)
 
 EXPORTS = ("ppn_version", "ppn_error_string", "ppn_last_hip_error", "ppn_polyfit_table", "ppn_edage_paths",
            "ppn_edage_paths_ex", "ppn_edage_paths_ex2", "ppn_edage_maps", "ppn_edage_maps_place", "ppn_edage_maps_raster",
@@ -63,7 +68,7 @@ EXPORTS = ("ppn_version", "ppn_error_string", "ppn_last_hip_error", "ppn_polyfit
            "ppn_upsample2x_nhwc_bwd", "ppn_upsample2x_concat_nhwc_bwd", "ppn_resize_concat_nhwc_bwd",
            "ppn_residual_layernorm_train_fwd", "ppn_residual_layernorm_bwd_workspace", "ppn_residual_layernorm_bwd",
            "ppn_patch_merge_ln_fwd", "ppn_patch_merge_ln_bwd_workspace", "ppn_patch_merge_ln_bwd", "ppn_patch_merge_ln_rows",
-           "ppn_patch_merge_ln_max_blocks")
+           "ppn_patch_merge_ln_max_blocks", "ppn_seg_tta")
 
 
 def _load():
@@ -184,6 +189,7 @@ def _load():
     lib.ppn_resize_ce_fwd.argtypes = [_p, _p, _p, _p, _p, _p, C.c_int64] + [C.c_int] * 9 + [_p]
     lib.ppn_resize_ce_bwd.argtypes = [_p, _p, _p, _p, _p] + [C.c_int] * 9 + [_p]
     lib.ppn_seg_eval.argtypes = [_p, _p, _p, _p] + [C.c_int] * 9 + [_p]
+    lib.ppn_seg_tta.argtypes = [C.POINTER(TtaAug), C.c_int, _p, _p] + [C.c_int] * 5 + [_p]
     lib.ppn_ohem_ce_workspace.argtypes = [C.c_int] * 3
     lib.ppn_ohem_ce_workspace.restype = C.c_int64
     lib.ppn_ohem_ce_fwd.argtypes = [_p] * 10 + [C.c_int64] + [C.c_int] * 8 + [C.c_float] + [C.c_int] * 3 + [_p]

@@ -156,3 +156,54 @@ def apply(aug, params, grid_or_rgb, labels, mean, std, dtype):
     if grid_or_rgb.dim() == 4 and grid_or_rgb.shape[-1] != 3:
         raise ValueError(f"augment.apply: [B,H,W,3] images, got {tuple(grid_or_rgb.shape)}")
     return _apply_cpu(params, grid_or_rgb, labels, mean, std, dtype, aug.out_size, aug.seg_pad_val)
+
+
+# ------------------------------------------------------------------------------------------------ test-time augmentation
+class MultiScaleFlipAug:
+    """mmseg's MultiScaleFlipAug (datasets/pipelines/test_time_aug.py) with the transforms of the reference's `--aug-test`
+    (SegNet/test.py:142-147: img_ratios [0.5, 0.75, 1.0, 1.25, 1.5, 1.75], flip True) for a batch on its device: calling it on a
+    normalised batch [B,3,H,W] — or on u8 occupancy codes [B,H,W], rendered with fused.grid_to_image (GPU) in `dtype` — returns
+    (imgs, img_metas), the two lists SegNet.forward(return_loss=False, img=imgs, img_metas=img_metas) takes.  Order as the
+    reference's loops (:112-115): scale-major, unflipped before flipped, one entry per direction.  Sizes are (int(H * ratio),
+    int(W * ratio)) (:73-75); an entry is F.interpolate(bilinear, align_corners=False) of the batch, then its flip.  Each entry's
+    metas (one dict per image) carry ori_shape, img_shape, pad_shape (H, W, 3 triples), scale_factor (float32 [4]: w, h, w, h),
+    flip and flip_direction.  Library ops only: a cold path of a dozen small resizes.
+
+    resize=False reproduces the test pipeline of configs/_base_/datasets/planning_seg.py as written: it has no Resize step, so under
+    `--aug-test` the ratios do not change the image — six ratios give six equal copies, each unflipped and flipped, and the merged
+    result is plain flip averaging."""
+
+    def __init__(self, img_ratios=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), flip=True, flip_direction="horizontal", resize=True):
+        self.img_ratios = [float(r) for r in (img_ratios if isinstance(img_ratios, (list, tuple)) else [img_ratios])]
+        self.flip = bool(flip)
+        self.flip_direction = list(flip_direction) if isinstance(flip_direction, (list, tuple)) else [flip_direction]
+        self.resize = bool(resize)
+        if not self.img_ratios or min(self.img_ratios) <= 0:
+            raise ValueError(f"MultiScaleFlipAug: img_ratios {self.img_ratios}")
+        if any(d not in ("horizontal", "vertical") for d in self.flip_direction):
+            raise ValueError(f"MultiScaleFlipAug: flip_direction {self.flip_direction}")
+
+    def __len__(self):
+        return len(self.img_ratios) * (2 if self.flip else 1) * len(self.flip_direction)
+
+    def __call__(self, img, dtype=torch.float32):
+        if img.dtype == torch.uint8 and img.dim() == 3:
+            from .dense import IMG_MEAN, IMG_STD
+            img = fused.grid_to_image(img, IMG_MEAN, IMG_STD, dtype)
+        if img.dim() != 4 or not img.is_floating_point():
+            raise ValueError(f"MultiScaleFlipAug: a normalised batch [B,3,H,W] or u8 codes [B,H,W], got {img.dtype} {tuple(img.shape)}")
+        B, ch, H, W = img.shape
+        imgs, img_metas = [], []
+        for ratio in self.img_ratios:
+            h, w = (int(H * ratio), int(W * ratio)) if self.resize else (H, W)
+            if h < 1 or w < 1:
+                raise ValueError(f"MultiScaleFlipAug: ratio {ratio} of {H} x {W} is empty")
+            scaled = img if (h, w) == (H, W) else torch.nn.functional.interpolate(img, (h, w), mode="bilinear", align_corners=False)
+            for flip in ([False, True] if self.flip else [False]):
+                for direction in self.flip_direction:
+                    imgs.append(scaled.flip(3 if direction == "horizontal" else 2) if flip else scaled)
+                    meta = {"ori_shape": (H, W, ch), "img_shape": (h, w, ch), "pad_shape": (h, w, ch),
+                            "scale_factor": np.array([w / W, h / H, w / W, h / H], dtype=np.float32), "flip": flip,
+                            "flip_direction": direction}
+                    img_metas.append([dict(meta) for _ in range(B)])
+        return imgs, img_metas

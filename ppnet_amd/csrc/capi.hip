@@ -538,6 +538,32 @@ int ppn_seg_eval(const void* logit, const void* label, uint8_t* pred, int64_t* a
     return PPN_OK;
 }
 
+int ppn_seg_tta(const ppn_tta_aug* augs, int n_augs, uint8_t* pred, float* prob, int B, int C, int H, int W, int logit_dtype, void* stream) {
+    if (!augs || n_augs < 1 || n_augs > PPN_SEG_TTA_MAX_AUGS) return PPN_E_INVALID;
+    if ((!pred && !prob) || (logit_dtype != 0 && logit_dtype != 1)) return PPN_E_INVALID;             // either output may be NULL, not both
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || C > ppn::seg_tta_max_classes()) return PPN_E_INVALID;
+    if (C > PPN_SEG_TTA_REG_CLASSES && !prob) return PPN_E_INVALID;                                    // prob is the accumulator
+    if (((uintptr_t)prob & 3) != 0) return PPN_E_INVALID;
+    // B H W and B C H W < 2^31, in steps that each stay within 64 bits
+    const long long HW = (long long)H * W;
+    if (HW >= 0x80000000LL || (long long)B * HW >= 0x80000000LL || (long long)C * HW >= 0x80000000LL ||
+        (long long)B * ((long long)C * HW) >= 0x80000000LL)
+        return PPN_E_INVALID;
+    for (int a = 0; a < n_augs; ++a) {
+        const ppn_tta_aug& g = augs[a];
+        if (!g.logit || ((uintptr_t)g.logit & 15) != 0 || g.flip < 0 || g.flip > 2) return PPN_E_INVALID;
+        if (g.h <= 0 || g.w <= 0 || g.hm <= 0 || g.wm <= 0) return PPN_E_INVALID;
+        const long long hw = (long long)g.h * g.w;
+        if (hw >= 0x80000000LL || (long long)C * hw >= 0x80000000LL || (long long)B * ((long long)C * hw) >= 0x80000000LL) return PPN_E_INVALID;
+    }
+    // work-items of the launch: a workgroup per tile of pixels
+    const long long px = ppn::seg_tta_pixels(), tiles = ((long long)B * HW + px - 1) / px;
+    if (tiles * ppn::seg_tta_threads() >= 0x7fffffffLL) return PPN_E_INVALID;
+    const int e = ppn::seg_tta_launch(augs, n_augs, pred, prob, B, C, H, W, logit_dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int64_t ppn_ohem_ce_workspace(int B, int H, int W) {
     if (ppn_resize_ce_workspace(B, H, W) < 0) return -1;                                               // the same limits on B, H, W
     return ppn::ohem_ce_workspace_bytes();

@@ -202,6 +202,13 @@ int seg_eval_max_groups();
 int seg_eval_max_classes();
 int seg_eval_launch(const void* logit, const void* label, uint8_t* pred, int64_t* areas, int B, int C, int h, int w, int H, int W, int ignore_index,
                     int logit_dtype, int label_dtype, hipStream_t stream);
+// seg_tta.hip: the merge of a multi-scale + flip test-time augmentation — per augmentation two composed bilinear resizes, softmax and
+// un-flip, then the mean and its argmax — in one launch; pixels per tile, work-items per workgroup (one workgroup per tile) and the
+// largest C (pred is uint8).  Taps and interp: resize_tap.h.  augs is a host array, passed on as one by-value kernel argument
+int seg_tta_pixels();
+int seg_tta_threads();
+int seg_tta_max_classes();
+int seg_tta_launch(const ppn_tta_aug* augs, int n_augs, uint8_t* pred, float* prob, int B, int C, int H, int W, int logit_dtype, hipStream_t stream);
 // ohem_ce.hip: resize_ce.hip's loss with online hard example mining (a radix select of the k-th score) and class weights, forward and
 // backward; pixels per tile, work-items per workgroup, the largest grid (a workgroup strides over the tiles) and the workspace (bytes,
 // the same for every size).  mode 0 = no sampler, 1 = threshold on the label's probability, 2 = the batch_kept largest losses.

@@ -131,12 +131,17 @@ class SegEvaluator:
         self.num_classes, self.ignore_index = int(num_classes), int(ignore_index)
         self.areas = None                                        # int64 [3, C] on the device of the first update
 
-    def update(self, model_or_logits, img, gt):
+    def update(self, model_or_logits, img, gt, aug=None):
         """model_or_logits: a SegNet (img its input batch) or a head's logits [B,C,h,w] at any resolution (img None); gt the labels
-        [B,H,W] / [B,1,H,W].  Returns this batch's areas (on the device, not synchronised)."""
+        [B,H,W] / [B,1,H,W].  aug (a SegNet only): an augment.MultiScaleFlipAug — the prediction is the test-time augmentation's merge
+        (SegNet.eval_areas).  Returns this batch's areas (on the device, not synchronised)."""
         if isinstance(model_or_logits, torch.Tensor):
+            if aug is not None:
+                raise ValueError("SegEvaluator.update: test-time augmentation needs the model, not its logits")
             g = gt.squeeze(1) if gt.dim() == 4 else gt
             a = heads.resized_eval_areas(model_or_logits, g if g.dtype == torch.uint8 else g.long(), self.ignore_index)
+        elif aug is not None:
+            a = model_or_logits.eval_areas(img, gt, self.ignore_index, aug=aug)
         else:
             a = model_or_logits.eval_areas(img, gt, self.ignore_index)
         if a.shape != (3, self.num_classes):

@@ -1196,6 +1196,63 @@ def seg_eval(logit, labels, ignore_index=255, want_pred=False):
     return areas, pred
 
 
+# ---------------------------------------------------------------- test-time augmentation: resizes + softmax + un-flip + mean + argmax
+TTA_CALLS = {"fwd": 0}                   # launches of ppn_seg_tta (like EVAL_CALLS)
+SEG_TTA_MAX_AUGS = 16                    # augmentations of one launch (include/ppnet_hip.h: PPN_SEG_TTA_MAX_AUGS)
+SEG_TTA_REG_CLASSES = 8                  # C up to here sums in registers; above, prob is the accumulator (PPN_SEG_TTA_REG_CLASSES)
+SEG_TTA_LDS_CLASSES = 64                 # C up to here the accumulating kernel keeps a pixel's logits in LDS; above, it interpolates thrice
+SEG_TTA_THREADS = 256                    # work-items per workgroup of csrc/seg_tta.hip
+SEG_TTA_PIXELS = 1024                    # pixels per tile: four consecutive ones per work-item
+SEG_TTA_MAX_CLASSES = 256                # pred is uint8
+_TTA_FLIP = {None: 0, "horizontal": 1, "vertical": 2}
+
+
+def seg_tta_ok(logits, mids, flips, out_hw):
+    """Whether ppn_seg_tta takes these: 1 to 16 CUDA float32 / bfloat16 logits [B,C,h_a,w_a] of one dtype, device, B and C <= 256, as
+    many (hm, wm) >= 1 and flips of None / 'horizontal' / 'vertical', sizes inside the entry point's limits (include/ppnet_hip.h)."""
+    if not 1 <= len(logits) <= SEG_TTA_MAX_AUGS or len(mids) != len(logits) or len(flips) != len(logits):
+        return False
+    x0 = logits[0]
+    if not (x0.is_cuda and x0.dtype in _DT and x0.dim() == 4):
+        return False
+    for x, mid, fl in zip(logits, mids, flips):
+        if not (x.is_cuda and x.device == x0.device and x.dtype == x0.dtype and x.dim() == 4 and x.shape[:2] == x0.shape[:2]):
+            return False
+        if min(x.shape) < 1 or x.numel() >= _INT32_END or len(mid) != 2 or min(mid) < 1 or max(mid) >= _INT32_END or fl not in _TTA_FLIP:
+            return False
+    B, C = x0.shape[:2]
+    return len(out_hw) == 2 and min(out_hw) >= 1 and C <= SEG_TTA_MAX_CLASSES and B * C * out_hw[0] * out_hw[1] < _INT32_END
+
+
+def seg_tta(logits, mids, flips, out_hw, want_prob=False):
+    """(pred, prob) of a test-time augmentation's merge (mmseg's aug_test): per augmentation a the head's low-resolution logits
+    logits[a] [B,C,h_a,w_a] (float32 / bfloat16) resized bilinearly (align_corners=False) to mids[a] = (hm, wm), the augmentation's
+    image size, and from there to out_hw = (H, W); softmax; flipped back where flips[a] is 'horizontal' / 'vertical' (None: not);
+    the mean over the augmentations; pred uint8 [B,H,W] its argmax (ties to the lowest class, a NaN never wins) and prob float32
+    [B,C,H,W] the mean itself, or None (want_prob False and C <= 8: above, the kernel accumulates in prob and it is returned).  One
+    ppn_seg_tta launch, float32 throughout, no full-resolution logits; nothing is read back: no host synchronisation."""
+    if not all(x.is_cuda for x in logits):
+        raise RuntimeError("ppnet_amd.fused: GPU tensors only (no CPU fallback)")
+    if not seg_tta_ok(logits, mids, flips, out_hw):
+        raise ValueError(f"seg_tta: {len(logits)} logits {[tuple(x.shape) for x in logits]} {sorted({str(x.dtype) for x in logits})} / "
+                         f"sizes {list(mids)} -> {tuple(out_hw)} / flips {list(flips)} are outside ppn_seg_tta's types and limits")
+    logits = [x.detach().contiguous() for x in logits]
+    B, C = logits[0].shape[:2]
+    H, W = int(out_hw[0]), int(out_hw[1])
+    dev = logits[0].device
+    augs = (L.TtaAug * len(logits))()
+    for g, x, mid, fl in zip(augs, logits, mids, flips):
+        g.logit, g.h, g.w, g.hm, g.wm, g.flip = x.data_ptr(), x.shape[2], x.shape[3], int(mid[0]), int(mid[1]), _TTA_FLIP[fl]
+    pred = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    prob = torch.empty(B, C, H, W, dtype=torch.float32, device=dev) if want_prob or C > SEG_TTA_REG_CLASSES else None
+    with torch.cuda.device(dev):
+        rc = L.lib.ppn_seg_tta(augs, len(logits), _p(pred), _p(prob), B, C, H, W, _DT[logits[0].dtype],
+                               ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    L.check(rc, "ppn_seg_tta")
+    TTA_CALLS["fwd"] += 1
+    return pred, prob
+
+
 # ---------------------------------------------------------------- the heads' training loss with a pixel sampler and class weights
 OHEM_CALLS = {"fwd": 0, "bwd": 0}        # launches of ppn_ohem_ce_fwd / ppn_ohem_ce_bwd (like LOSS_CALLS, which they leave alone)
 OHEM_THREADS = 256                       # work-items per workgroup of every kernel of csrc/ohem_ce.hip

@@ -671,6 +671,28 @@ def resized_eval_areas(logit_lowres, gt, ignore_index=255, align_corners=False):
         return eval_areas(logit.argmax(1), gt, logit.shape[1], ignore_index)
 
 
+def tta_mean_prob(logits, mids, flips, out_hw):
+    """The mean class probabilities [B,C,H,W] of a test-time augmentation (mmseg's aug_test, encoder_decoder.py:200-285) from the
+    heads' low-resolution logits, in torch ops: per augmentation logits[a] [B,C,h_a,w_a] resized bilinearly (align_corners=False) to
+    mids[a] = (hm, wm), the augmentation's image size, and from there to out_hw = (H, W); softmax over the classes; flipped back along
+    W for flips[a] == 'horizontal', along H for 'vertical' (None: not); summed in index order and divided by the number of
+    augmentations.  Everything in the logits' dtype promoted to at least float32, nothing rounded in between — ppn_seg_tta's
+    definition (fused.seg_tta), on any device."""
+    if not len(logits) == len(mids) == len(flips) or not logits:
+        raise ValueError(f"tta_mean_prob: {len(logits)} logits, {len(mids)} sizes, {len(flips)} flips")
+    total = None
+    for x, mid, fl in zip(logits, mids, flips):
+        if fl not in (None, "horizontal", "vertical"):
+            raise ValueError(f"tta_mean_prob: flip {fl!r}")
+        x = x.to(torch.promote_types(x.dtype, torch.float32))
+        x = F.interpolate(x, tuple(mid), mode="bilinear", align_corners=False)
+        p = F.softmax(F.interpolate(x, tuple(out_hw), mode="bilinear", align_corners=False), dim=1)
+        if fl is not None:
+            p = p.flip(dims=(3,) if fl == "horizontal" else (2,))
+        total = p if total is None else total + p
+    return total / len(logits)
+
+
 def dice_loss(logit_fullres, gt, smooth=1.0, exponent=2, class_weight=None, loss_weight=1.0, ignore_index=255):
     """mmseg's DiceLoss.forward (losses/dice_loss.py:12-47,92-123) for full-resolution logits [B,C,H,W] and labels [B,H,W], in torch
     ops: any dtype, any exponent, CPU or GPU.  p = softmax(logit, 1), tc = the labels clamped into [0, C - 1], v = the label is valid;

@@ -25,6 +25,12 @@ from .swin import SwinTransformer
 from .vit import VisionTransformer
 
 
+# Class counts from which aug_test merges with the library composition by default: ppn_seg_tta is the faster side where a pixel's logits
+# stay in registers or LDS (12 augmentations to 16 x 512^2: 1.7-2.3 x at C = 2, 1.6 x at C = 19) and the slower one above (0.6 x float32,
+# 0.4 x bfloat16 at C = 150; tools/seg_tta_timing.py).  PPNET_LIBRARY_TTA_FROM_C overrides, read at call time.
+LIBRARY_TTA_FROM_C = fused.SEG_TTA_LDS_CLASSES + 1
+
+
 class SegNet(nn.Module):
     """EncoderDecoder(test_cfg=mode 'whole') (SegNet/mmseg/models/segmentors/encoder_decoder.py:16-265, base.py:62-112): the
     constructor takes the reference's config sub-dicts (`from_config` the whole `model=dict(...)`), `forward` the reference
@@ -165,11 +171,53 @@ class SegNet(nn.Module):
             raise ValueError(f"num of augmentations ({len(imgs)}) != num of image meta ({len(img_metas)})")
         if len(imgs) == 1:
             return self.simple_test(imgs[0], img_metas[0], rescale)
-        assert rescale                                                       # aug_test, encoder_decoder.py:274-276
+        return self.aug_test(imgs, img_metas, rescale)
+
+    def aug_test(self, imgs, img_metas, rescale=True):
+        """encoder_decoder.py:267-285: the labels of the mean, over the augmentations, of `inference`'s probabilities; one int64 array
+        per image.  CUDA inputs without autograd, at most fused.SEG_TTA_MAX_AUGS augmentations of one ori_shape, C <= 256 and
+        align_corners False on model and head: the head runs once per augmentation and its LOW-resolution logits go to one
+        ppn_seg_tta launch (fused.seg_tta: both resizes, softmax, un-flip, mean and argmax in float32; no full-resolution tensor but
+        the uint8 labels).  PPNET_LIBRARY_TTA=1 (read at call time), CPU tensors and everything else take the composition of
+        `inference` calls as it always ran — and so does C >= LIBRARY_TTA_FROM_C by default: above fused.SEG_TTA_LDS_CLASSES the kernel
+        interpolates every logit three times and is the slower side; PPNET_LIBRARY_TTA_FROM_C=257 opts in."""
+        return list(self.aug_labels(imgs, img_metas, rescale).to(torch.int64).cpu().numpy())
+
+    def aug_labels(self, imgs, img_metas, rescale=True):
+        """aug_test's labels as a tensor [B,H,W] on the inputs' device: uint8 from the kernel, int64 from the composition."""
+        assert rescale                                                       # encoder_decoder.py:274-276
+        merged = self._aug_test_fused(imgs, img_metas)
+        if merged is not None:
+            return merged
         prob = self.inference(imgs[0], img_metas[0], rescale)
         for x, m in zip(imgs[1:], img_metas[1:]):
             prob = prob + self.inference(x, m, rescale)
-        return list((prob / len(imgs)).argmax(dim=1).cpu().numpy())
+        return (prob / len(imgs)).argmax(dim=1)
+
+    def _aug_test_fused(self, imgs, img_metas):
+        """aug_test's labels as uint8 [B,H,W] from one ppn_seg_tta launch, or None where that path does not apply."""
+        classes = self.decode_head.conv_seg.out_channels
+        if (torch.is_grad_enabled() or os.environ.get("PPNET_LIBRARY_TTA") or not all(x.is_cuda for x in imgs)
+                or len(imgs) > fused.SEG_TTA_MAX_AUGS or self.align_corners or self.decode_head.align_corners
+                or classes > fused.SEG_TTA_MAX_CLASSES or classes >= int(os.environ.get("PPNET_LIBRARY_TTA_FROM_C", LIBRARY_TTA_FROM_C))):
+            return None
+        mids, flips, sizes = [], [], set()
+        for x, m in zip(imgs, img_metas):
+            metas = _meta(m) if m else [{}]
+            ori = metas[0].get("ori_shape")
+            assert all(mm.get("ori_shape") == ori for mm in metas)
+            mids.append(tuple(x.shape[-2:]))                                 # encode_decode's resize target
+            sizes.add(tuple(ori[:2]) if ori is not None else mids[-1])
+            d = metas[0].get("flip_direction", "horizontal") if metas[0].get("flip", False) else None
+            assert d in (None, "horizontal", "vertical")
+            flips.append(d)
+        if len(sizes) != 1:
+            return None                                                      # (the composition's own add raises)
+        logits = [self.decode_head(self.backbone(x)) for x in imgs]
+        out_hw = sizes.pop()
+        if not fused.seg_tta_ok(logits, mids, flips, out_hw):
+            return None                                                      # a dtype or size outside the kernel's
+        return fused.seg_tta(logits, mids, flips, out_hw)[0]
 
     def simple_test(self, img, img_meta, rescale=True):
         """encoder_decoder.py:254-265.  Unflipped whole-image inference at the input size on the GPU takes the fused tail
@@ -221,16 +269,24 @@ class SegNet(nn.Module):
         return losses
 
     @torch.no_grad()
-    def eval_areas(self, img, gt_semantic_seg, ignore_index=255):
+    def eval_areas(self, img, gt_semantic_seg, ignore_index=255, aug=None):
         """The area histograms that mmseg's evaluation sums over a dataset (intersect_and_union of the whole-image prediction,
         core/evaluation/metrics.py:26-86): int64 [3, C] on img's device — intersect | prediction | label per class, for
         evaluate.total_area_to_metrics.  Labels as in forward_train ([B,1,H,W] or [B,H,W]; uint8 as they are).  With labels of the
         input's size the head's output goes to heads.resized_eval_areas in its own resolution and dtype — one kernel on the GPU
         (ppn_seg_eval: no [B,C,H,W] logits, no softmax, no int64 argmax, no masks); labels of another size get encode_decode's
-        resize to the input size, then the resize to the labels (encoder_decoder.py:247-252) and the library composition."""
+        resize to the input size, then the resize to the labels (encoder_decoder.py:247-252) and the library composition.
+        aug, an augment.MultiScaleFlipAug: the prediction is aug_labels' merge over aug(img) (on the GPU one ppn_seg_tta launch) at the
+        input's size, which the labels must have; the areas are heads.eval_areas of it."""
         gt = gt_semantic_seg.squeeze(1) if gt_semantic_seg.dim() == 4 else gt_semantic_seg
         if gt.dtype != torch.uint8:
             gt = gt.long()
+        if aug is not None:
+            imgs, metas = aug(img)
+            pred = self.aug_labels(imgs, metas) if len(imgs) > 1 else self.inference(imgs[0], metas[0]).argmax(dim=1)
+            if tuple(pred.shape) != tuple(gt.shape):
+                raise ValueError(f"eval_areas with test-time augmentation: labels {tuple(gt.shape)} for predictions {tuple(pred.shape)}")
+            return eval_areas(pred, gt, self.decode_head.conv_seg.out_channels, ignore_index)
         if tuple(gt.shape[-2:]) == tuple(img.shape[-2:]):
             return resized_eval_areas(self.decode_head(self.backbone(img)), gt, ignore_index, align_corners=self.align_corners)
         logit = F.interpolate(self.encode_decode(img).float(), gt.shape[-2:], mode="bilinear", align_corners=self.align_corners)

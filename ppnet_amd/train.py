@@ -210,12 +210,13 @@ def evaluate_gennet(model, mask_space, mask_path):
         return F.mse_loss(out.squeeze(1).float(), mask_path.to(torch.float32) / 255.0)
 
 
-def evaluate_segnet(segnet, grid_u8, mask_space, batch=16, metrics=("mIoU",)):
+def evaluate_segnet(segnet, grid_u8, mask_space, batch=16, metrics=("mIoU",), aug=None):
     """The reference's evaluation hook (evaluation = dict(metric='mIoU'), configs/_base_/schedules; mmseg/core/evaluation/
     metrics.py) of the eval-mode network over generated pairs: grid_u8 [n,R,R] occupancy codes (or normalised images [n,3,R,R]),
     mask_space [n,R,R] labels, `batch` images at a time.  One ppn_seg_eval per batch on the GPU, areas summed on the device (and
-    over the ranks of an initialised process group), one read-back at the end.  Returns evaluate.total_area_to_metrics' dict; the
-    network's training flag is restored."""
+    over the ranks of an initialised process group), one read-back at the end.  aug, an augment.MultiScaleFlipAug: the reference's
+    `--aug-test` — every batch's prediction is the merge over its augmentations (SegNet.aug_labels: one ppn_seg_tta per batch on the
+    GPU).  Returns evaluate.total_area_to_metrics' dict; the network's training flag is restored."""
     from . import evaluate, fused
     from .segnet import IMG_MEAN, IMG_STD
     net = segnet.module if isinstance(segnet, nn.parallel.DistributedDataParallel) else segnet
@@ -227,7 +228,7 @@ def evaluate_segnet(segnet, grid_u8, mask_space, batch=16, metrics=("mIoU",)):
     try:
         for i in range(0, grid_u8.shape[0], batch):
             g = grid_u8[i:i + batch]
-            ev.update(net, fused.grid_to_image(g, IMG_MEAN, IMG_STD, dtype) if g.dtype == torch.uint8 else g, mask_space[i:i + batch])
+            ev.update(net, fused.grid_to_image(g, IMG_MEAN, IMG_STD, dtype) if g.dtype == torch.uint8 else g, mask_space[i:i + batch], aug=aug)
     finally:
         net.train(was_training)
     return ev.all_reduce().compute(metrics)

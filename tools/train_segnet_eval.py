@@ -36,7 +36,7 @@ def chain_eval(torch, mask_u8, pb, mb, placements, R, gen):
                                  pb.length.repeat_interleave(placements) * (R / 50.0))
 
 
-def evaluate(torch, net, dev, R, gen, paths_n=16, placements=8, seed=987654321):
+def evaluate(torch, net, dev, R, gen, paths_n=16, placements=8, seed=987654321, tta=None):
     from ppnet_amd import edage, evaluate as EV, fused, train
     from ppnet_amd.segnet import IMG_MEAN, IMG_STD
     pb = edage.generate_paths(paths_n, R, 50.0, 3.0, seed=seed, device=dev)
@@ -58,6 +58,9 @@ def evaluate(torch, net, dev, R, gen, paths_n=16, placements=8, seed=987654321):
            "corridor_fraction_gt": float((gt == 1).float().mean()), "corridor_fraction_pred": float((lab == 1).float().mean())}
     out["chain_segnet_labels"] = chain_eval(torch, lab, pb, mb, placements, R, gen)
     out["chain_label_masks"] = chain_eval(torch, gt, pb, mb, placements, R, gen)
+    if tta is not None:                # the reference's --aug-test: the merged prediction of the multi-scale + flip list (one ppn_seg_tta per batch)
+        mt = train.evaluate_segnet(net, grid, space, batch=16, metrics=("mIoU",), aug=tta)
+        out["mIoU_aug_test"], out["pixel_acc_aug_test"] = EV.summarize(mt)["mIoU"], float(mt["aAcc"])
     return out
 
 
@@ -76,6 +79,8 @@ def main():
                     help="train on the reference's train_pipeline (flip + photometric distortion, ppnet_amd.augment) instead of the bare palette image")
     ap.add_argument("--dice-weight", type=float, default=None, metavar="W",
                     help="train on loss_decode=[CrossEntropyLoss, DiceLoss(loss_weight=W)] (ppn_resize_dice_fwd / _bwd) instead of cross-entropy alone")
+    ap.add_argument("--aug-test", action="store_true",
+                    help="score the final evaluation under the reference's test-time augmentation too (augment.MultiScaleFlipAug(): ratios 0.5 .. 1.75 x flip)")
     args = ap.parse_args()
     from ppnet_amd import augment, edage, train
     from ppnet_amd.gennet import AEViT, load_trained
@@ -125,7 +130,7 @@ def main():
             emit({"step": it, "wall_s": round(time.time() - t0, 1), "train_loss": round(loss_acc / max(n_acc, 1), 4),
                   **{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}})
             loss_acc, n_acc = 0.0, 0
-    r = evaluate(torch, net, dev, R, gen)
+    r = evaluate(torch, net, dev, R, gen, tta=augment.MultiScaleFlipAug() if args.aug_test else None)
     emit({"step": it, "final": True, "wall_s": round(time.time() - t0, 1), "images_seen": it * batch, "images_per_s": round(it * batch / (time.time() - t0), 1),
           **{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}})
 
