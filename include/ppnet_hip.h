@@ -541,8 +541,11 @@ int ppn_na2d_bwd_vpad(const void* qkv, const void* pad_kv, const float* rpb, con
 /* Fused residual + LayerScale + LayerNorm around the NAT layer's dense ops (SegNet/nat.py:140-153):
  *   a == NULL : y_out = LayerNorm(x)                                   (x_out ignored)
  *   a != NULL : x_out = x + gamma * a  (gamma NULL = 1);  y_out = LayerNorm(x_out) unless y_out is NULL.
- * rows x C row-major, C a multiple of 8 with C/8 a power of two <= 64, or C = 1024, or any C <= 64; w, b, gamma are [C] in the
- * same dtype (0 = float32, 1 = bfloat16; statistics in float32). x_out may alias x. */
+ * rows x C row-major, C a multiple of 8 with C/8 a power of two <= 64 (one pass of C/8 lanes), or C = 1024 (two passes of 64 lanes),
+ * or C/8 = 3 * 2^k with 2^k <= 64 (three passes of 2^k lanes: 96, 192, 384, 768, 1536 — and 24, 48 on the padded form), or any
+ * C <= 64 on the unpadded forms; every other width returns PPN_E_UNSUPPORTED before any launch, from this entry, from
+ * ppn_layernorm_offset and from ppn_residual_layernorm_padded alike.  w, b, gamma are [C] in the same dtype (0 = float32,
+ * 1 = bfloat16; statistics in float32). x_out may alias x. */
 int ppn_residual_layernorm(const void* x, const void* a, const void* gamma, const void* w, const void* b, void* x_out,
                            void* y_out, int64_t rows, int32_t C, float eps, int32_t dtype, void* stream);
 /* y_out = LayerNorm(x + xoff) with a per-channel float32 offset xoff [C] (NULL = none; float32 whatever dtype x has): for a residual stream whose constant

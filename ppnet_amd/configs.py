@@ -14,6 +14,42 @@ DINAT_BASE = dict(   # SegNet/configs/dinat/dinat_base.py:5-24 over _base_/model
                   dilations=[[1, 16, 1], [1, 4, 1, 8], [1, 2, 1, 3, 1, 4, 1, 2, 1, 3, 1, 4, 1, 2, 1, 3, 1, 4], [1, 2, 1, 2, 1]]),
     decode_head=dict(in_channels=1024, channels=512, num_convs=4, up_scale=2, num_classes=2, kernel_size=3))
 
+# DiNAT-L + SETR-UP, the reference's largest model: residual streams of 192 / 384 / 768 / 1536 channels, dilations up to 20.  It sets no
+# `layer_scale` (dinat_large.py:7-18; the base file has none either), so the layers have no LayerScale.  `pretrained` (an ImageNet-22k
+# checkpoint path on the authors' machine, dinat_large.py:16) is left out: load one with DiNAT.init_weights or load_state_dict.
+DINAT_LARGE = dict(   # SegNet/configs/dinat/dinat_large.py:5-24 over _base_/models/dinat.py:3-46
+    type="EncoderDecoder", pretrained=None,
+    backbone=dict(   # _base_/models/dinat.py:6-22 with dinat_large.py:7-18
+        type="DiNAT", embed_dim=192, mlp_ratio=2.0, depths=[3, 4, 18, 5], num_heads=[6, 12, 24, 48], drop_path_rate=0.3, kernel_size=7,
+        dilations=[[1, 20, 1], [1, 5, 1, 10], [1, 2, 1, 3, 1, 4, 1, 5, 1, 2, 1, 3, 1, 4, 1, 5, 1, 5], [1, 2, 1, 2, 1]],
+        out_indices=(0, 1, 2, 3), qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, in_patch_size=4, frozen_stages=-1),
+    decode_head=dict(   # _base_/models/dinat.py:23-43 with dinat_large.py:19-23
+        type="SETRUPHead", norm_layer=dict(type="LN", eps=1e-6, requires_grad=True), num_convs=4, up_scale=2, kernel_size=3,
+        init_cfg=[dict(type="Constant", val=1.0, bias=0, layer="LayerNorm"), dict(type="Normal", std=0.01, override=dict(name="conv_seg"))],
+        in_channels=1536, channels=512, in_index=-1, num_classes=2, norm_cfg=dict(type="SyncBN", requires_grad=True), align_corners=False,
+        loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0)),
+    train_cfg=dict(), test_cfg=dict(mode="whole"))
+
+# NAT-Mini + UPerHead: streams of 64 / 128 / 256 / 512 channels, mlp_ratio 3 (hidden widths 192 / 384 / 768 / 1536).  `pretrained` (a
+# checkpoint path on the authors' machine, upernet_nat_mini.py:16) is left out.
+NAT_MINI_UPER = dict(   # SegNet/configs/nat/upernet_nat_mini.py:6-34 over _base_/models/nat.py:3-37
+    type="EncoderDecoder", pretrained=None,
+    backbone=dict(   # _base_/models/nat.py:6-21 with upernet_nat_mini.py:7-17
+        type="NAT", embed_dim=64, mlp_ratio=3.0, depths=[3, 4, 6, 5], num_heads=[2, 4, 8, 16], drop_path_rate=0.2, kernel_size=7,
+        out_indices=(0, 1, 2, 3), qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, in_patch_size=4, frozen_stages=-1,
+        layer_scale=1e-5),
+    decode_head=dict(   # upernet_nat_mini.py:18-29
+        type="UPerHead", in_channels=[64, 128, 256, 512], in_index=[0, 1, 2, 3], pool_scales=(1, 2, 3, 6), channels=64, dropout_ratio=0.1,
+        num_classes=2, norm_cfg=dict(type="SyncBN", requires_grad=True), align_corners=False,
+        loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0)),
+    # _base_/models/nat.py:22-34 with upernet_nat_mini.py:30-33: in_channels 512 on in_index 2, although level 2 of NAT-Mini has 256
+    # channels — kept as the reference merges it (the override is upernet_nat_base.py's, where level 2 has 512; the auxiliary head runs
+    # in training only, which this config cannot do as written)
+    auxiliary_head=dict(type="FCNHead", in_channels=512, in_index=2, channels=256, num_convs=1, concat_input=False, dropout_ratio=0.1,
+                        num_classes=2, norm_cfg=dict(type="SyncBN", requires_grad=True), align_corners=False,
+                        loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=0.4)),
+    train_cfg=dict(), test_cfg=dict(mode="whole"))
+
 # Swin-B: SegNet/configs/_base_/models/swin.py:1-57 merged with configs/swin/swin_base.py:5-37 (SETR-UP) and
 # configs/swin/upernet_swin_base.py:5-38 (UPerHead + FCN auxiliary head).  `pretrained` (an ImageNet checkpoint path on the
 # authors' machine, swin_base.py:14) is left out: load a checkpoint with SwinTransformer.init_weights or load_state_dict.

@@ -4,8 +4,9 @@
 //   residual_ln_kernel    x' = x + gamma * a ;  y = LN(x')            (residual + LayerScale + the NEXT sub-layer's norm)
 //
 // The reference runs these as separate torch ops (mul, add, layer_norm = 7 tensor passes per sub-layer); fused they are
-// 4 (read x, read a, write x', write y).  A row of C channels (128..1024, every NAT/DiNAT level) is owned by C/8 lanes
-// (at most one wave), 8 elements per lane per pass = one 16-byte access for bf16; statistics in float32.
+// 4 (read x, read a, write x', write y).  A row of C channels (every NAT/DiNAT level: 64..1024 at embed 64 / 128, 192..1536 at
+// DiNAT-L's 192) is owned by a power-of-two number of lanes (at most one wave) that make one to three passes over it, 8 elements per
+// lane per pass = one 16-byte access for bf16; statistics in float32.
 #include <hip/hip_bf16.h>
 #include "ppn_device.h"
 #include "ppn_kernels.h"
@@ -15,7 +16,9 @@ namespace ppn {
 
 constexpr int NORM_ROW_ITERS = 8;     // row groups per wave: the per-channel vectors (w, b, offset: 5x the bytes of a bf16 row piece) are loaded once
 
-// PASSES = C / (8 * lpr): 1 for C <= 512, 2 for C = 1024.  RESID: fuse x' = x + gamma * a (gamma may be null = 1).
+// PASSES = C / (8 * lpr): 1 for C <= 512, 2 for C = 1024, 3 for C / 8 = 3 * 2^k (96 .. 1536; launch_norm holds the rule).  Pass p
+// of a row covers columns [p * 8 lpr, (p + 1) * 8 lpr): the row's lanes read one contiguous 16 lpr-byte run (bfloat16) per pass.
+// RESID: fuse x' = x + gamma * a (gamma may be null = 1).
 template <typename T, int PASSES, bool RESID>
 __global__ __launch_bounds__(256) void norm_kernel(const T* __restrict__ x, const T* __restrict__ a, const T* __restrict__ gamma,
                                                    const T* __restrict__ w, const T* __restrict__ b, T* __restrict__ x_out,
@@ -532,16 +535,24 @@ static int launch_norm(const void* x, const void* a, const void* gamma, const vo
 #undef PPN_ROWS
         return (int)hipGetLastError();
     }
-    int lpr = C / 8, passes = 1;
-    if (lpr > 64) { passes = lpr / 64; lpr = 64; }
-    if (passes > 2 || (lpr & (lpr - 1)) != 0 || lpr * 8 * passes != C) return -1;
+    // C = 8 * lpr * passes, lpr a power of two <= 64: one pass up to 512, two of 64 lanes at 1024, three where C / 8 = 3 * 2^k
+    // (24 and 48 on the padded form, 96, 192, 384, 768, 1536: DiNAT-L's streams and NAT-Mini's hidden widths)
+    const int g = C / 8;
+    const auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+    int lpr, passes;
+    if (C % 8 != 0) return -1;
+    if (pow2(g) && g <= 64) { passes = 1; lpr = g; }
+    else if (g == 128) { passes = 2; lpr = 64; }
+    else if (g % 3 == 0 && pow2(g / 3) && g / 3 <= 64) { passes = 3; lpr = g / 3; }
+    else return -1;
     const long long rows_per_block = 4LL * (64 / lpr) * NORM_ROW_ITERS;
     const dim3 grid((unsigned)((rows + rows_per_block - 1) / rows_per_block));
     const bool resid = a != nullptr;
 #define PPN_NORM_LAUNCH(P, R) hipLaunchKernelGGL((norm_kernel<T, P, R>), grid, dim3(256), 0, stream, (const T*)x, (const T*)a, \
     (const T*)gamma, (const T*)w, (const T*)b, (T*)x_out, (T*)y_out, rows, C, lpr, eps, Hr, Wr, Hp, Wp, (const float*)xoff)
     if (passes == 1) { if (resid) PPN_NORM_LAUNCH(1, true); else PPN_NORM_LAUNCH(1, false); }
-    else { if (resid) PPN_NORM_LAUNCH(2, true); else PPN_NORM_LAUNCH(2, false); }
+    else if (passes == 2) { if (resid) PPN_NORM_LAUNCH(2, true); else PPN_NORM_LAUNCH(2, false); }
+    else { if (resid) PPN_NORM_LAUNCH(3, true); else PPN_NORM_LAUNCH(3, false); }
 #undef PPN_NORM_LAUNCH
     return (int)hipGetLastError();
 }

@@ -228,7 +228,10 @@ class _ResidualLayerNormFunction(torch.autograd.Function):
 def layer_norm(x, ln, pad_to=None, offset=None):
     """y = ln(x) for a torch.nn.LayerNorm over the last dimension. pad_to=(Hp,Wp): x is [B,H,W,C] and y is the
     zero-padded (bottom/right) [B,Hp,Wp,C] grid the next neighbourhood attention wants.  offset [C]: y = ln(x + offset)
-    (a residual stream whose constant part is carried outside the tensor, ppn_layernorm_offset)."""
+    (a residual stream whose constant part is carried outside the tensor, ppn_layernorm_offset).
+    Widths of the inference kernels (outside autograd; csrc/fused_norm.hip launch_norm): multiples of 8 up to 64 (without pad_to), then
+    C / 8 = 2^k up to 64 lanes (128, 256, 512), 1024, and C / 8 = 3 * 2^k (96, 192, 384, 768, 1536: DiNAT-L's levels, and 24 / 48 with
+    pad_to); any other width raises PpnError(PPN_E_UNSUPPORTED).  The recorded pair keeps NORM_WIDTHS."""
     if recording(x, ln.weight, ln.bias):
         if pad_to is None and offset is None and x.numel() >= NORM_RECORD_MIN and _norm_kernels_record(x, None, None, ln, None):
             return _ResidualLayerNormFunction.apply(x, None, None, None, ln.weight, ln.bias, ln.eps)
@@ -253,13 +256,20 @@ def layer_norm(x, ln, pad_to=None, offset=None):
 
 _LN_REFUSED = set()        # (width, dtype) pairs the LayerNorm kernels answered with PPN_E_UNSUPPORTED
 
+# Widths layer_norm_any_width keeps on the framework's LayerNorm although the kernel takes them: 768 is ViT-B's token width (every
+# LayerNorm of vit.py) and the SETR-UP head's norm on its 768-channel features, which ran there while the kernel refused the width.
+# Moving ViT-B onto the kernel is a follow-up of its own: it needs an A/B at ViT-B's shapes and a re-measurement of the label
+# agreement tests/test_gpu_vit.py pins.  Nothing else reads this set: fused.layer_norm at 768 (DiNAT-L's level 2) runs the kernel.
+LN_FRAMEWORK_WIDTHS = frozenset({768})
+
 
 def layer_norm_any_width(x, ln):
     """ln(x) over the last dimension on the LayerNorm kernel; a row width the kernel does not take (it answers PPN_E_UNSUPPORTED
-    before any launch: csrc/fused_norm.hip launch_norm, widths up to 512 and 1024 — not ViT-B's 768) runs on the framework's
-    LayerNorm instead, and the refusal is remembered."""
+    before any launch: csrc/fused_norm.hip launch_norm takes C / 8 = 2^k up to 64, 128, and 3 * 2^k up to 1536) runs on the
+    framework's LayerNorm instead, and the refusal is remembered.  So does a width of LN_FRAMEWORK_WIDTHS (ViT-B's 768), without asking
+    the kernel."""
     key = (x.shape[-1], x.dtype)
-    if key not in _LN_REFUSED:
+    if key[0] not in LN_FRAMEWORK_WIDTHS and key not in _LN_REFUSED:
         try:
             return layer_norm(x, ln)
         except L.PpnError as e:
@@ -273,7 +283,8 @@ def residual_layer_norm(x, a, gamma, ln_next, pad_to=None, scale=None):
     """x' = x + scale[b] * gamma * a (gamma None = 1; scale None = 1) in place of x; returns (x', ln_next(x')) — y is None when ln_next
     is None.  scale: float32 [B], the per-image stochastic-depth factor (0 = dropped, 1 / keep otherwise) of a training step.
     Under autograd x' is a new tensor and the HIP training pair is recorded (_ResidualLayerNormFunction); CPU tensors, mixed dtypes,
-    other widths, pad_to and PPNET_LIBRARY_NORM=1 compose the torch ops then."""
+    widths outside NORM_WIDTHS (DiNAT-L's 192 / 384 / 768 / 1536 among them), pad_to and PPNET_LIBRARY_NORM=1 compose the torch ops
+    then.  Outside autograd the widths are layer_norm's: one to three passes of the inference kernel, 8 .. 1536."""
     if recording(x, a, gamma, *((ln_next.weight, ln_next.bias) if ln_next is not None else ())):
         if pad_to is None and _norm_kernels_record(x, a, gamma, ln_next, scale):
             w, b = (ln_next.weight, ln_next.bias) if ln_next is not None else (None, None)

@@ -267,10 +267,13 @@ class NATBlock(nn.Module):
         """The level runs on ppn_nat_gemm_bf16 (csrc/mfma_gemm.h): folded bfloat16 inference, C and the MLP width multiples of
         256, whole 256-token tiles — and at least 64 of them in the narrowest projection (tokens x C): the persistent kernels walk
         256 x 256 tiles one per CU, and a batch of 1-16 problems has a handful (a level-2 projection at batch 1 is TWO tiles, each
-        walking K alone: 34 us where the wave-per-block kernel of gemm_small.hip behind a LayerNorm launch takes 12)."""
+        walking K alone: 34 us where the wave-per-block kernel of gemm_small.hip behind a LayerNorm launch takes 12).  The stream is
+        at most 1024 wide (ppn_row_stats_bf16) with at most 4 row-statistic partials (ppn_nat_gemm_bf16): DiNAT-L's level 3
+        (C = 1536, 6 partials) takes the per-layer folded path, LayerNorm kernel + accumulating library GEMM."""
         b0 = self.blocks[0]
         C = x.shape[-1]
         return (b0.folded and x.is_cuda and x.dtype == torch.bfloat16 and b0.attn.qkv.weight.dtype == torch.bfloat16 and C % 256 == 0
+                and C <= 1024 and fused.nat_partials(C) <= 4
                 and (x.numel() // C) % 256 == 0 and (x.numel() // C // 256) * (C // 256) >= int(os.environ.get("PPNET_SMALL_GEMM_TILES", "64")) and b0.mlp.fc1.out_features % 256 == 0 and b0.mlp._erf_gelu() and x.is_contiguous()
                 and not torch.is_grad_enabled() and not library_width(C) and not os.environ.get("PPNET_NO_LN_FOLD"))
 
@@ -344,7 +347,7 @@ class NAT(nn.Module):
         self.embed_dim = embed_dim
         self.num_features = [int(embed_dim * 2 ** i) for i in range(self.num_levels)]
         self.patch_embed = ConvTokenizer(in_chans, embed_dim, norm_layer)
-        dpr = [float(v) for v in torch.linspace(0, drop_path_rate, sum(depths))]      # nat.py:247
+        dpr = [float(v) for v in torch.linspace(0, drop_path_rate, sum(depths), device="cpu")]      # nat.py:247 (values: never on meta)
         self.levels = nn.ModuleList(
             NATBlock(int(embed_dim * 2 ** i), depths[i], num_heads[i], kernel_size,
                      None if dilations is None else dilations[i], downsample=(i < self.num_levels - 1),

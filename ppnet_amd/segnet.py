@@ -10,8 +10,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import fused
-from .configs import (DINAT_BASE, DINATS_BASE_SETRUP, NAT_BASE_UPER, NAT_BASE_UPERPUP, SWIN_BASE_SETRUP, SWIN_BASE_UPER, SWIN_BASE_UPERPUP,  # noqa: F401
-                      VIT_BASE_SETRUP, _SWIN_BASE_BACKBONE, _SWIN_NORM_CFG, _UPERPUP_AUX)
+from .configs import (DINAT_BASE, DINAT_LARGE, DINATS_BASE_SETRUP, NAT_BASE_UPER, NAT_BASE_UPERPUP, NAT_MINI_UPER, SWIN_BASE_SETRUP,  # noqa: F401
+                      SWIN_BASE_UPER, SWIN_BASE_UPERPUP, VIT_BASE_SETRUP, _SWIN_BASE_BACKBONE, _SWIN_NORM_CFG, _UPERPUP_AUX)
 from .dense import (IMG_MEAN, IMG_STD, LIBRARY_GEMM_BELOW_C, LIBRARY_GEMM_FROM_C, drop_path, normalize_images)  # noqa: F401
 from .dense import accumulate as _accumulate, bias32 as _bias32, library_width as _library_width, linear as _linear  # noqa: F401
 from .dense import mfma_weights as _mfma_weights, own_gemm_ok as _own_gemm_ok, use_mfma_conv as _use_mfma_conv  # noqa: F401
@@ -134,6 +134,9 @@ class SegNet(nn.Module):
         """argmax labels as u8 [B,R,R].  SETR-UP head with two classes on the GPU: the x2 up-sampling of the logits, the
         resize to the input size, softmax and argmax are one HIP kernel (ppn_seg_labels_2class); otherwise forward()."""
         head = self.decode_head
+        if img.dtype == torch.uint8 and isinstance(self.backbone, NAT) and not self.backbone.patch_embed.takes_codes(img):
+            # a NAT tokenizer the palette kernels do not serve (float32 weights, an embed width other than 128 — DiNAT-L, NAT-Mini): render
+            img = fused.grid_to_image(img, IMG_MEAN, IMG_STD, next(self.parameters()).dtype)
         if (img.is_cuda and isinstance(head, SETRUPHead) and head.conv_seg.out_channels == 2 and not self.align_corners
                 and not head.align_corners and head.up_convs[-1][1].scale_factor == 2.0):
             return fused.seg_labels_2class(head(self.backbone(img), lowres=True), img.shape[-2:])
