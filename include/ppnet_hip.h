@@ -73,7 +73,8 @@ extern "C" {
  * ppn_ohem_ce_bwd joined at 111 in the same way, and so did ppn_resize_dice_workspace, ppn_resize_dice_fwd and ppn_resize_dice_bwd, and
  * ppn_upsample2x_nhwc_bwd, ppn_upsample2x_concat_nhwc_bwd and ppn_resize_concat_nhwc_bwd, and ppn_residual_layernorm_train_fwd,
  * ppn_residual_layernorm_bwd_workspace and ppn_residual_layernorm_bwd, and ppn_patch_merge_ln_fwd, ppn_patch_merge_ln_bwd_workspace,
- * ppn_patch_merge_ln_bwd, ppn_patch_merge_ln_rows and ppn_patch_merge_ln_max_blocks, and ppn_seg_tta. */
+ * ppn_patch_merge_ln_bwd, ppn_patch_merge_ln_rows and ppn_patch_merge_ln_max_blocks, and ppn_seg_tta, and ppn_gennet_stem_train_workspace,
+ * ppn_gennet_stem_train_fwd, ppn_gennet_stem_train_bwd, ppn_gennet_stem_train_tile and ppn_gennet_stem_train_max_blocks. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -617,6 +618,43 @@ int64_t ppn_patch_merge_ln_bwd_workspace(int B, int H, int W, int C);   /* bytes
 int     ppn_patch_merge_ln_bwd(const void* gy, const void* x, const float* stats, const void* gamma, void* workspace,
                                void* dx, void* dgamma /* may be NULL */, void* dbeta /* may be NULL */,
                                int B, int H, int W, int C, int dtype, void* stream);
+
+/* The training pair of GenNet's stem (csrc/gennet_stem_train.hip; reference GenNet/networks/ae_vit.py conv_first): Conv2d(1, C, 3, 1, 1) ->
+ * BatchNorm2d on the batch statistics -> LeakyReLU at full resolution, forward and backward, in one write of z and one read of dz.
+ *
+ * x [B][H][W] float32 (one input channel); w [C][9] (tap 3 dy + dx), bias, gamma, beta [C] float32; z and dz [B][C][H][W] contiguous NCHW
+ * of `dtype` (0 = float32, 1 = bfloat16).  N = B H W.  All arithmetic is float32 from the float32 x and parameters, the moments and the
+ * two finishing steps float64; bfloat16 is only the rounding of z on store and the widening of dz on load.
+ * ppn_gennet_stem_train_fwd: with p(n) the zero-padded 3 x 3 patch of x at pixel n, moments [54] float64 receives S1 = sum_n p (9) and
+ *   the lower triangle of S2 = sum_n p p^T (45, element (i, j <= i) at 9 + i (i + 1) / 2 + j), summed in float64 — one partial per
+ *   workgroup in `workspace`, added in a fixed order.  stats [3][C] float32 receives mean_c = w_c . S1 / N + bias_c, the biased variance
+ *   var_c = w_c^T (S2 / N - S1 S1^T / N^2) w_c and rstd_c = 1 / sqrt(var_c + eps).  z = leaky_relu(gamma ((conv(x) + bias - mean) rstd)
+ *   + beta, negative_slope), rounded once.  The convolution's output is never written.
+ * ppn_gennet_stem_train_bwd: recomputes xhat and the pre-activation u from x with the forward's own instructions (the LeakyReLU mask
+ *   is the forward's bit for bit), g = dz (u > 0 ? 1 : negative_slope); dbeta_c = sum g, dgamma_c = sum g xhat and, with G_c = sum g p,
+ *   dw_c = gamma_c rstd_c (G_c - (dbeta_c / N) S1 - (dgamma_c / N) X_c), X_c = rstd_c (S2 w_c + (bias_c - mean_c) S1), each [C] or [C][9]
+ *   float32.  The sums are float32 per workgroup (one partial each in `workspace`), added in a fixed order and finished in float64, rounded
+ *   once: one writer per element, two calls give the same bits.  The gradient of bias is exactly 0 and is not written.  x, w, bias, gamma,
+ *   beta, stats and moments as in (and from) the forward.
+ * ppn_gennet_stem_train_workspace(B, H, W, C): the bytes `workspace` holds (either call),
+ *   max(54 * 8, C * 11 * 4) * min(ceil(N / ppn_gennet_stem_train_tile()), ppn_gennet_stem_train_max_blocks()); < 0 for sizes the entry
+ *   points refuse.
+ * ppn_gennet_stem_train_tile(): the pixels of one workgroup tile (1024: 256 work-items x 4 consecutive pixels).
+ * ppn_gennet_stem_train_max_blocks(): the most workgroups (in x) of the summing kernels; past that many tiles a workgroup strides.
+ *
+ * C in {8, 16, 24, 32}.  Before any HIP call: PPN_E_INVALID for a NULL required pointer, a pointer that is not 16-byte aligned
+ * (moments: 8, stats: 4), an extent below 1 or N < 2, a dtype outside {0, 1}, an eps or negative_slope that is negative or not finite,
+ * 2^31 elements and more in z; PPN_E_UNSUPPORTED for another C. */
+int     ppn_gennet_stem_train_tile(void);
+int     ppn_gennet_stem_train_max_blocks(void);
+int64_t ppn_gennet_stem_train_workspace(int B, int H, int W, int C);   /* bytes; < 0 for invalid sizes */
+int     ppn_gennet_stem_train_fwd(const float* x, const float* w, const float* bias /* may be NULL = 0 */, const float* gamma,
+                                  const float* beta, void* z, float* stats, double* moments, void* workspace,
+                                  int B, int H, int W, int C, float eps, float negative_slope, int dtype, void* stream);
+int     ppn_gennet_stem_train_bwd(const void* dz, const float* x, const float* w, const float* bias /* may be NULL = 0 */,
+                                  const float* gamma, const float* beta, const float* stats, const double* moments, void* workspace,
+                                  float* dw, float* dgamma, float* dbeta,
+                                  int B, int H, int W, int C, float negative_slope, int dtype, void* stream);
 
 /* Bilinear x2 up-sampling of an NHWC tensor x [B][H][W][C] -> y [B][2H][2W][C] with PyTorch's
  * F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) arithmetic (the SETR-UP head's Upsample,

@@ -775,6 +775,62 @@ int ppn_patch_merge_ln_bwd(const void* gy, const void* x, const float* stats, co
     return PPN_OK;
 }
 
+// what the three stem-training entry points check alike: extents, the pixel count, the channel set, z's element count
+static int stem_train_sizes(int B, int H, int W, int C) {
+    if (B < 1 || H < 1 || W < 1 || C < 1) return PPN_E_INVALID;
+    if ((long long)B * H > 0x7fffffffLL || (long long)B * H * W > 0x7fffffffLL) return PPN_E_INVALID;     // overflow-safe in this order
+    if ((long long)B * H * W < 2) return PPN_E_INVALID;                       // one value per channel has no batch variance
+    if (!ppn::gennet_stem_channels_ok(C)) return PPN_E_UNSUPPORTED;           // C outside {8, 16, 24, 32}
+    if ((long long)B * H * W * C >= 0x80000000LL) return PPN_E_INVALID;       // z: 2^31 elements or more
+    return PPN_OK;
+}
+
+static bool stem_scalar_ok(float v) { return v >= 0.0f && v <= 3.0e38f; }     // not NaN, not negative, not inf
+
+int64_t ppn_gennet_stem_train_workspace(int B, int H, int W, int C) {
+    if (stem_train_sizes(B, H, W, C) != PPN_OK) return -1;
+    return ppn::gennet_stem_train_workspace_bytes((long long)B * H * W, C);
+}
+
+int ppn_gennet_stem_train_fwd(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, void* z, float* stats,
+                              double* moments, void* workspace, int B, int H, int W, int C, float eps, float negative_slope, int dtype,
+                              void* stream) {
+    if (!x || !w || !gamma || !beta || !z || !stats || !moments || !workspace) return PPN_E_INVALID;     // bias may be NULL: none
+    if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)z | (uintptr_t)workspace) & 15) != 0 ||
+        ((uintptr_t)moments & 7) != 0 || ((uintptr_t)stats & 3) != 0)
+        return PPN_E_INVALID;
+    if (dtype != 0 && dtype != 1) return PPN_E_INVALID;
+    if (!stem_scalar_ok(eps) || !stem_scalar_ok(negative_slope)) return PPN_E_INVALID;
+    const int ok = stem_train_sizes(B, H, W, C);
+    if (ok != PPN_OK) return ok;
+    const int e = ppn::gennet_stem_train_fwd_launch(x, w, bias, gamma, beta, z, stats, moments, workspace, B, H, W, C, eps, negative_slope, dtype,
+                                                    (hipStream_t)stream);
+    if (e == -1) return PPN_E_UNSUPPORTED;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_gennet_stem_train_bwd(const void* dz, const float* x, const float* w, const float* bias, const float* gamma, const float* beta,
+                              const float* stats, const double* moments, void* workspace, float* dw, float* dgamma, float* dbeta, int B, int H,
+                              int W, int C, float negative_slope, int dtype, void* stream) {
+    if (!dz || !x || !w || !gamma || !beta || !stats || !moments || !workspace || !dw || !dgamma || !dbeta) return PPN_E_INVALID;
+    if ((((uintptr_t)dz | (uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)workspace | (uintptr_t)dw |
+          (uintptr_t)dgamma | (uintptr_t)dbeta) & 15) != 0 || ((uintptr_t)moments & 7) != 0 || ((uintptr_t)stats & 3) != 0)
+        return PPN_E_INVALID;
+    if (dtype != 0 && dtype != 1) return PPN_E_INVALID;
+    if (!stem_scalar_ok(negative_slope)) return PPN_E_INVALID;
+    const int ok = stem_train_sizes(B, H, W, C);
+    if (ok != PPN_OK) return ok;
+    const int e = ppn::gennet_stem_train_bwd_launch(dz, x, w, bias, gamma, beta, stats, moments, workspace, dw, dgamma, dbeta, B, H, W, C,
+                                                    negative_slope, dtype, (hipStream_t)stream);
+    if (e == -1) return PPN_E_UNSUPPORTED;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_gennet_stem_train_tile(void) { return ppn::gennet_stem_tile(); }
+int ppn_gennet_stem_train_max_blocks(void) { return ppn::gennet_stem_max_blocks(); }
+
 int ppn_upsample2x_nhwc(const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t relu, int32_t dtype,
                         void* stream) {
     return ppn_upsample2x_nhwc_bias(x, nullptr, y, B, H, W, C, relu, dtype, stream);

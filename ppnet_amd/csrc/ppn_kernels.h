@@ -143,6 +143,19 @@ int patch_merge_ln_fwd_launch(const void* x, const void* gamma, const void* beta
 int patch_merge_ln_bwd_launch(const void* gy, const void* x, const float* stats, const void* gamma, float* workspace, void* dx, void* dgamma,
                               void* dbeta, int B, int H, int W, int C, int dtype, hipStream_t stream);
 
+// gennet_stem_train.hip: the training pair of GenNet's stem (Conv2d(1, C, 3, 1, 1) + BatchNorm2d on batch statistics + LeakyReLU), C in
+// {8, 16, 24, 32}; pixels per workgroup tile, the workgroup cap of the reducing kernels, the workspace in bytes for n = B H W pixels
+// (-1 = not taken).  Launches: -1 = a channel count the kernels do not take
+int gennet_stem_channels_ok(int C);
+int gennet_stem_tile();
+int gennet_stem_max_blocks();
+long long gennet_stem_train_workspace_bytes(long long n, int C);
+int gennet_stem_train_fwd_launch(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, void* z, float* stats,
+                                 double* moments, void* workspace, int B, int H, int W, int C, float eps, float slope, int dtype, hipStream_t stream);
+int gennet_stem_train_bwd_launch(const void* dz, const float* x, const float* w, const float* bias, const float* gamma, const float* beta,
+                                 const float* stats, const double* moments, void* workspace, float* dw, float* dgamma, float* dbeta, int B, int H, int W,
+                                 int C, float slope, int dtype, hipStream_t stream);
+
 int resize_concat_launch(const void* const* x, const int* hw, const int* ch, int n, void* out, int B, int dtype, hipStream_t stream);
 int adaptive_pools_launch(const void* x, void* const* y, const int* scales, int n, int B, int H, int W, int C, int dtype, hipStream_t stream);
 int upsample2x_launch(const void* x, const void* bias, const void* add, void* y, int B, int H, int W, int C, int relu, int dtype, hipStream_t stream);

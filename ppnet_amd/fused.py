@@ -7,7 +7,9 @@ the functions without a backward kernel compose differentiable torch ops instead
 attentions': neighbourhood (ppn_na2d_bwd, na.na2d_autograd), ViT's global one (ppn_mhsa_bwd, vit.mhsa_autograd) and Swin's window one
 (ppn_swin_wmsa_bwd, swin.wmsa_autograd) — the heads' loss: bilinear resize + cross-entropy (ppn_resize_ce_bwd,
 resize_cross_entropy below) — and the heads' bilinear up-sampling (ppn_upsample2x_nhwc_bwd, ppn_upsample2x_concat_nhwc_bwd,
-ppn_resize_concat_nhwc_bwd: upsample2x_nhwc, upsample2x_add, upsample2x_concat and resize_concat record their own kernels)."""
+ppn_resize_concat_nhwc_bwd: upsample2x_nhwc, upsample2x_add, upsample2x_concat and resize_concat record their own kernels) — and
+GenNet's stem, convolution + BatchNorm on batch statistics + LeakyReLU (ppn_gennet_stem_train_fwd / ppn_gennet_stem_train_bwd,
+stem_bn_act at the end of this file)."""
 import ctypes
 import os
 
@@ -1601,3 +1603,128 @@ def patch_merge_ln(x, ln):
     if recording(x, ln.weight, ln.bias):
         return _PatchMergeLNFunction.apply(x.to(dt), ln.weight.to(dt), ln.bias.to(dt), ln.eps)
     return _pm_fwd(x.to(dt).contiguous(), ln.weight.detach().to(dt).contiguous(), ln.bias.detach().to(dt).contiguous(), ln.eps, False)[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------- GenNet stem training
+STEM_CALLS = {"fwd": 0, "bwd": 0}        # launches of ppn_gennet_stem_train_fwd / ppn_gennet_stem_train_bwd (like MERGE_CALLS)
+STEM_CHANNELS = frozenset({8, 16, 24, 32})                                  # csrc/gennet_stem_train.hip: the set ppn_conv3x3_c1_nhwc takes
+STEM_THREADS = 256                       # work-items per workgroup of every kernel of csrc/gennet_stem_train.hip
+STEM_LINE = 4                            # consecutive pixels per work-item: the unit of its vector loads and stores
+STEM_TILE = 1024                         # pixels per workgroup tile (ppn_gennet_stem_train_tile)
+STEM_MAX_BLOCKS = 512                    # workgroups at most in x of the summing kernels (ppn_gennet_stem_train_max_blocks)
+STEM_MOMENTS = 54                        # float64 moments of the 3 x 3 patches: S1 (9), the lower triangle of S2 (45)
+STEM_SUMS = 11                           # float32 sums per channel of the backward: g, g xhat, g p_0 .. g p_8
+
+
+def stem_train_workspace_bytes(B, H, W, C):
+    """ppn_gennet_stem_train_workspace's formula (include/ppnet_hip.h): per workgroup one [54] float64 partial forward, one [C][11] float32
+    partial backward, in the same buffer."""
+    return max(STEM_MOMENTS * 8, C * STEM_SUMS * 4) * min(-(-(B * H * W) // STEM_TILE), STEM_MAX_BLOCKS)
+
+
+def library_stem():
+    """PPNET_LIBRARY_STEM=1 (read at call time, like PPNET_LIBRARY_MERGE): stem_bn_act takes Conv2d + BatchNorm2d + LeakyReLU and the
+    framework's backwards instead of the HIP pair."""
+    return bool(os.environ.get("PPNET_LIBRARY_STEM"))
+
+
+def stem_train_ok(x, conv, bn):
+    """Whether stem_bn_act runs conv -> bn -> LeakyReLU on the HIP pair: x a contiguous CUDA float32 [B,1,H,W] that does not require grad
+    (the kernels have no input gradient) with B H W >= 2 (one value per channel is torch's own ValueError) and fewer than 2^31 outputs;
+    conv exactly a Conv2d(1, C, 3, 1, 1), dilation 1, groups 1, zero padding, C in STEM_CHANNELS; bn exactly a BatchNorm2d (a SyncBatchNorm
+    reduces over ranks) in training mode, affine, tracking running statistics with a float momentum; float32 parameters and buffers on
+    x's device, autograd recording a parameter; no autocast or bfloat16 autocast; and the knob off.  Everything else keeps the library."""
+    if library_stem() or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 1 or x.requires_grad:
+        return False
+    if type(conv) is not torch.nn.Conv2d or type(bn) is not torch.nn.BatchNorm2d:
+        return False
+    if (conv.in_channels != 1 or conv.out_channels not in STEM_CHANNELS or conv.kernel_size != (3, 3) or conv.stride != (1, 1)
+            or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 or conv.padding_mode != "zeros"):
+        return False
+    if not (bn.training and bn.affine and bn.track_running_stats and isinstance(bn.momentum, float) and bn.num_features == conv.out_channels):
+        return False
+    B, _, H, W = x.shape
+    if B * H * W < 2 or B * H * W * conv.out_channels >= 2 ** 31 or not x.is_contiguous():
+        return False
+    tensors = (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    if any(t is not None and (t.dtype != torch.float32 or t.device != x.device) for t in tensors) or bn.running_mean is None:
+        return False
+    if torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") != torch.bfloat16:
+        return False
+    return recording(conv.weight, conv.bias, bn.weight, bn.bias)
+
+
+def _stem_workspace(B, H, W, C, dev):
+    need = L.lib.ppn_gennet_stem_train_workspace(B, H, W, C)
+    if need < 0:
+        raise L.PpnError(f"ppn_gennet_stem_train_workspace refuses B {B} H {H} W {W} C {C}", -1)
+    return torch.empty(max(need, 16) // 4, dtype=torch.float32, device=dev)
+
+
+def _stem_fwd(x, w, b, gamma, beta, eps, slope, dtype):
+    """ppn_gennet_stem_train_fwd on contiguous float32 tensors (x [B,1,H,W] or [B,H,W], w [C,1,3,3] or [C,9], b None = no bias):
+    (z [B,C,H,W] of dtype, stats [3,C] float32, moments [54] float64)."""
+    B, H, W, C = x.shape[0], x.shape[-2], x.shape[-1], w.shape[0]
+    z = torch.empty(B, C, H, W, dtype=dtype, device=x.device)
+    stats = torch.empty(3, C, dtype=torch.float32, device=x.device)
+    moments = torch.empty(STEM_MOMENTS, dtype=torch.float64, device=x.device)
+    ws = _stem_workspace(B, H, W, C, x.device)
+    with torch.cuda.device(x.device):
+        rc = L.lib.ppn_gennet_stem_train_fwd(_p(x), _p(w), _p(b), _p(gamma), _p(beta), _p(z), _p(stats), _p(moments), _p(ws), B, H, W, C,
+                                             float(eps), float(slope), _DT[dtype], _stream(x))
+    L.check(rc, "ppn_gennet_stem_train_fwd")
+    STEM_CALLS["fwd"] += 1
+    return z, stats, moments
+
+
+def _stem_bwd(dz, x, w, b, gamma, beta, stats, moments, slope):
+    """ppn_gennet_stem_train_bwd on contiguous tensors: (dw shaped like w, dgamma [C], dbeta [C]), float32."""
+    B, H, W, C = x.shape[0], x.shape[-2], x.shape[-1], w.shape[0]
+    dw, dgamma, dbeta = torch.empty_like(w), torch.empty_like(gamma), torch.empty_like(beta)
+    ws = _stem_workspace(B, H, W, C, x.device)
+    with torch.cuda.device(x.device):
+        rc = L.lib.ppn_gennet_stem_train_bwd(_p(dz), _p(x), _p(w), _p(b), _p(gamma), _p(beta), _p(stats), _p(moments), _p(ws), _p(dw), _p(dgamma),
+                                             _p(dbeta), B, H, W, C, float(slope), _DT[dz.dtype], _stream(x))
+    L.check(rc, "ppn_gennet_stem_train_bwd")
+    STEM_CALLS["bwd"] += 1
+    return dw, dgamma, dbeta
+
+
+class _StemTrainFunction(torch.autograd.Function):
+    """(z, stats) = LeakyReLU(BatchNorm_train(conv3x3(x))) on ppn_gennet_stem_train_fwd / ppn_gennet_stem_train_bwd.  Saved: x, the
+    parameters, the statistics [3,C] and the moments [54] — nothing of z's size.  x gets no gradient; the convolution bias gets zeros
+    (its gradient is the sum of a BatchNorm input gradient: exactly 0), not None — DistributedDataParallel waits for every parameter."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, eps, slope, dtype):
+        w, gamma, beta = w.detach().contiguous(), gamma.detach().contiguous(), beta.detach().contiguous()
+        b = b.detach().contiguous() if b is not None else None
+        z, stats, moments = _stem_fwd(x, w, b, gamma, beta, eps, slope, dtype)
+        ctx.save_for_backward(x, w, b, gamma, beta, stats, moments)
+        ctx.slope = slope
+        ctx.mark_non_differentiable(stats)
+        return z, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, _dstats):
+        x, w, b, gamma, beta, stats, moments = ctx.saved_tensors
+        dw, dgamma, dbeta = _stem_bwd(dz.contiguous(), x, w, b, gamma, beta, stats, moments, ctx.slope)
+        return None, dw, torch.zeros_like(b) if b is not None else None, dgamma, dbeta, None, None, None
+
+
+def stem_bn_act(x, conv, bn, negative_slope):
+    """leaky_relu(bn(conv(x))) for GenNet's stem.  Where stem_train_ok holds, the HIP pair: z is written once in the CUDA autocast dtype
+    (float32 without autocast) and the backward is one pass over dz; bn's running statistics are updated as
+    F.batch_norm does in training (momentum, the unbiased variance N / (N - 1)) and num_batches_tracked counts the call.  Otherwise the
+    library composition, untouched."""
+    if not stem_train_ok(x, conv, bn):
+        return F.leaky_relu(bn(conv(x)), negative_slope)
+    dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
+    z, stats = _StemTrainFunction.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.eps, float(negative_slope), dtype)
+    with torch.no_grad():
+        n, m = x.shape[0] * x.shape[2] * x.shape[3], bn.momentum
+        bn.num_batches_tracked.add_(1)
+        bn.running_mean.mul_(1.0 - m).add_(stats[0], alpha=m)
+        bn.running_var.mul_(1.0 - m).add_(stats[1], alpha=m * n / (n - 1))
+    return z

@@ -251,7 +251,14 @@ class AEViT(nn.Module):
             for blk in self.enc_conv[1:]:
                 x = blk(x)
         else:
-            x = self.conv_first(x)
+            cf = self.conv_first
+            if (isinstance(cf, nn.Sequential) and len(cf) == 3 and type(cf[2]) is nn.LeakyReLU and fused.stem_train_ok(x, cf[0], cf[1])):
+                # GPU training of the unprepared stem: conv + BatchNorm (batch statistics) + LeakyReLU as one write of z and one read
+                # of dz (ppn_gennet_stem_train_fwd / ppn_gennet_stem_train_bwd; stem_from_moments below is the algebra).
+                # PPNET_LIBRARY_STEM (read at call time) keeps the three library ops.
+                x = fused.stem_bn_act(x, cf[0], cf[1], cf[2].negative_slope)
+            else:
+                x = cf(x)
             for blk in self.enc_conv:
                 x = blk(x)
         B, C, H, W = x.shape
@@ -281,6 +288,33 @@ class AEViT(nn.Module):
             wf, bf = self._final_pack()                                      # dim -> 1 at full resolution: direct HIP kernel
             return fused.conv3x3_to1(x, wf, bf)
         return c(x)
+
+
+def stem_from_moments(x, dz, w, b, gamma, beta, eps, slope):
+    """The algebra of the stem's training kernels (csrc/gennet_stem_train.hip) in torch ops, in the inputs' dtype,
+    on any device: z = leaky_relu(BatchNorm_train(conv3x3(x) + b)) and the parameter gradients for an upstream dz, with the batch
+    statistics from the 54 moments of the input's 3 x 3 patches and the backward from per-channel sums — neither pass forms a
+    gradient of y's size.  x [B,H,W] or [B,1,H,W]; dz [B,C,H,W]; w [C,1,3,3] or [C,9]; b [C] or None; gamma, beta [C].
+    Returns (z, mean, biased var, dW shaped like w, dgamma, dbeta); the gradient of b is exactly 0."""
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    C, N = w.shape[0], x.shape[0] * x.shape[-2] * x.shape[-1]
+    w9 = w.reshape(C, 9)
+    b = torch.zeros(C, dtype=x.dtype, device=x.device) if b is None else b
+    p = F.unfold(x.reshape(B, 1, H, W), 3, padding=1).transpose(1, 2).reshape(N, 9)      # zero-padded patches, tap 3 dy + dx
+    S1, S2 = p.sum(0), p.t() @ p                                                      # one pass over the 1-channel input
+    m = S1 / N
+    cov = S2 / N - torch.outer(m, m)
+    mean, var = w9 @ m + b, ((w9 @ cov) * w9).sum(1)
+    rstd = torch.rsqrt(var + eps)
+    xh = (p @ w9.t() + (b - mean)) * rstd                                             # [N, C], recomputed by the backward
+    u = gamma * xh + beta
+    z = torch.where(u > 0, u, u * slope).reshape(B, H, W, C).permute(0, 3, 1, 2)
+    g = dz.permute(0, 2, 3, 1).reshape(N, C)
+    g = torch.where(u > 0, g, g * slope)
+    dbeta, dgamma, G = g.sum(0), (g * xh).sum(0), g.t() @ p                           # 11 sums per channel
+    X = rstd[:, None] * (w9 @ S2 + (b - mean)[:, None] * S1)                          # sum xhat p, from the moments
+    dW = (gamma * rstd)[:, None] * (G - (dbeta / N)[:, None] * S1 - (dgamma / N)[:, None] * X)
+    return z, mean, var, dW.reshape(w.shape), dgamma, dbeta
 
 
 AE = AEViT      # predict.py:12 `from networks import AEViT as AE`
