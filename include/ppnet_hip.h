@@ -74,7 +74,9 @@ extern "C" {
  * ppn_upsample2x_nhwc_bwd, ppn_upsample2x_concat_nhwc_bwd and ppn_resize_concat_nhwc_bwd, and ppn_residual_layernorm_train_fwd,
  * ppn_residual_layernorm_bwd_workspace and ppn_residual_layernorm_bwd, and ppn_patch_merge_ln_fwd, ppn_patch_merge_ln_bwd_workspace,
  * ppn_patch_merge_ln_bwd, ppn_patch_merge_ln_rows and ppn_patch_merge_ln_max_blocks, and ppn_seg_tta, and ppn_gennet_stem_train_workspace,
- * ppn_gennet_stem_train_fwd, ppn_gennet_stem_train_bwd, ppn_gennet_stem_train_tile and ppn_gennet_stem_train_max_blocks. */
+ * ppn_gennet_stem_train_fwd, ppn_gennet_stem_train_bwd, ppn_gennet_stem_train_tile and ppn_gennet_stem_train_max_blocks, and
+ * ppn_gennet_tail_train_workspace, ppn_gennet_tail_train_fwd, ppn_gennet_tail_train_bwd, ppn_gennet_tail_train_tile and
+ * ppn_gennet_tail_train_max_blocks. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -654,6 +656,44 @@ int     ppn_gennet_stem_train_fwd(const float* x, const float* w, const float* b
 int     ppn_gennet_stem_train_bwd(const void* dz, const float* x, const float* w, const float* bias /* may be NULL = 0 */,
                                   const float* gamma, const float* beta, const float* stats, const double* moments, void* workspace,
                                   float* dw, float* dgamma, float* dbeta,
+                                  int B, int H, int W, int C, float negative_slope, int dtype, void* stream);
+
+/* The training pair of GenNet's tail (csrc/gennet_tail_train.hip; reference GenNet/networks/ae_vit.py, the last dec_conv stage's BatchNorm2d
+ * and LeakyReLU followed by conv_final): BatchNorm2d on the batch statistics -> LeakyReLU -> Conv2d(C, 1, 3, 1, 1) at full resolution,
+ * forward and backward, in two reads of y forward and two reads of y plus one write of dy backward.  Neither the BatchNorm's output, the
+ * activation z nor its gradient is ever written.
+ *
+ * y and dy [B][C][H][W], out and dout [B][1][H][W], contiguous NCHW of `dtype` (0 = float32, 1 = bfloat16); gamma, beta [C], wf [C][9]
+ * (tap 3 dy + dx), bf [1], stats [3][C] and every parameter gradient float32.  N = B H W.  All arithmetic is float32 (the statistics and
+ * the two finishing steps float64); bfloat16 is only the widening of y and dout on load and the rounding of out and dy on store.
+ * ppn_gennet_tail_train_fwd: stats receives mean_c = sum y / N, the biased variance var_c = sum y^2 / N - mean_c^2 (never negative; 0
+ *   exactly for a constant plane) and rstd_c = 1 / sqrt(var_c + eps), from float64 sums — one partial per workgroup in `workspace`, added
+ *   in a fixed order.  With xhat = (y - mean) rstd, u = gamma xhat + beta and z = u > 0 ? u : negative_slope u inside the image and
+ *   z = 0 outside it (the convolution's zero padding): out(p) = bf + sum_c sum_tap wf[c][tap] z_c(p + tap), rounded once.
+ * ppn_gennet_tail_train_bwd: recomputes xhat and u from y with the forward's own instructions (the LeakyReLU mask is the forward's bit
+ *   for bit).  With d = dout, zero outside the image: dz_c(q) = sum_tap wf[c][tap] d(q - tap), g = dz (u > 0 ? 1 : negative_slope);
+ *   dbeta_c = sum g, dgamma_c = sum g xhat, dwf[c][tap] = sum_q z_c(q) d(q - tap), dbf = sum d (not written when dbf is NULL), and
+ *   dy = gamma rstd (g - dbeta / N - xhat dgamma / N) in a second pass (skipped when dy is NULL).  The sums are float32 per workgroup
+ *   (one partial each in `workspace`), added in a fixed order and finished in float64, rounded once: one writer per element, no atomics,
+ *   two calls give the same bits.  y, gamma, beta, wf and stats as in (and from) the forward.
+ * ppn_gennet_tail_train_workspace(B, H, W, C): the bytes `workspace` holds (either call),
+ *   max(C * 2 * 8, (C * 11 + 1) * 4) * min(ceil(N / ppn_gennet_tail_train_tile()), ppn_gennet_tail_train_max_blocks()); < 0 for sizes the
+ *   entry points refuse.
+ * ppn_gennet_tail_train_tile(): the pixels of one workgroup tile (1024: 256 work-items x 4 consecutive pixels).
+ * ppn_gennet_tail_train_max_blocks(): the most workgroups (in x) of the summing kernels; past that many tiles a workgroup strides.
+ *
+ * C in {8, 16, 24, 32}.  Before any HIP call: PPN_E_INVALID for a NULL required pointer, a pointer that is not 16-byte aligned (stats,
+ * bf, dbf: 4), an extent below 1 or N < 2, a dtype outside {0, 1}, an eps or negative_slope that is negative or not finite, 2^31
+ * elements and more in y; PPN_E_UNSUPPORTED for another C. */
+int     ppn_gennet_tail_train_tile(void);
+int     ppn_gennet_tail_train_max_blocks(void);
+int64_t ppn_gennet_tail_train_workspace(int B, int H, int W, int C);   /* bytes; < 0 for invalid sizes */
+int     ppn_gennet_tail_train_fwd(const void* y, const float* gamma, const float* beta, const float* wf, const float* bf /* may be NULL = 0 */,
+                                  void* out, float* stats, void* workspace,
+                                  int B, int H, int W, int C, float eps, float negative_slope, int dtype, void* stream);
+int     ppn_gennet_tail_train_bwd(const void* dout, const void* y, const float* gamma, const float* beta, const float* wf, const float* stats,
+                                  void* workspace, void* dy /* may be NULL */, float* dgamma, float* dbeta, float* dwf,
+                                  float* dbf /* may be NULL */,
                                   int B, int H, int W, int C, float negative_slope, int dtype, void* stream);
 
 /* Bilinear x2 up-sampling of an NHWC tensor x [B][H][W][C] -> y [B][2H][2W][C] with PyTorch's

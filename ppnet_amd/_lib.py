@@ -70,7 +70,9 @@ EXPORTS = ("ppn_version", "ppn_error_string", "ppn_last_hip_error", "ppn_polyfit
            "ppn_patch_merge_ln_fwd", "ppn_patch_merge_ln_bwd_workspace", "ppn_patch_merge_ln_bwd", "ppn_patch_merge_ln_rows",
            "ppn_patch_merge_ln_max_blocks", "ppn_seg_tta",
            "ppn_gennet_stem_train_workspace", "ppn_gennet_stem_train_fwd", "ppn_gennet_stem_train_bwd", "ppn_gennet_stem_train_tile",
-           "ppn_gennet_stem_train_max_blocks")
+           "ppn_gennet_stem_train_max_blocks",
+           "ppn_gennet_tail_train_workspace", "ppn_gennet_tail_train_fwd", "ppn_gennet_tail_train_bwd", "ppn_gennet_tail_train_tile",
+           "ppn_gennet_tail_train_max_blocks")
 
 
 def _load():
@@ -164,6 +166,12 @@ def _load():
     lib.ppn_gennet_stem_train_bwd.argtypes = [_p] * 12 + [C.c_int] * 4 + [C.c_float, C.c_int, _p]
     lib.ppn_gennet_stem_train_tile.argtypes = []
     lib.ppn_gennet_stem_train_max_blocks.argtypes = []
+    lib.ppn_gennet_tail_train_workspace.argtypes = [C.c_int] * 4
+    lib.ppn_gennet_tail_train_workspace.restype = C.c_int64
+    lib.ppn_gennet_tail_train_fwd.argtypes = [_p] * 8 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_int, _p]
+    lib.ppn_gennet_tail_train_bwd.argtypes = [_p] * 12 + [C.c_int] * 4 + [C.c_float, C.c_int, _p]
+    lib.ppn_gennet_tail_train_tile.argtypes = []
+    lib.ppn_gennet_tail_train_max_blocks.argtypes = []
     lib.ppn_grid_to_image.argtypes = [_p, _p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, _p]
     lib.ppn_seg_labels_2class.argtypes = [_p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
     lib.ppn_bias_act_nhwc.argtypes = [_p, _p, C.c_int64, C.c_int32, C.c_float, C.c_int32, _p]
@@ -215,7 +223,7 @@ def _load():
         getattr(lib, name)
         if name not in ("ppn_error_string", "ppn_na2d_bwd_workspace", "ppn_na2d_bwd_vpad_workspace", "ppn_mhsa_bwd_workspace", "ppn_swin_wmsa_bwd_workspace",
                         "ppn_resize_ce_workspace", "ppn_ohem_ce_workspace", "ppn_resize_dice_workspace", "ppn_residual_layernorm_bwd_workspace",
-                        "ppn_patch_merge_ln_bwd_workspace", "ppn_gennet_stem_train_workspace"):
+                        "ppn_patch_merge_ln_bwd_workspace", "ppn_gennet_stem_train_workspace", "ppn_gennet_tail_train_workspace"):
             getattr(lib, name).restype = C.c_int
     return lib
 

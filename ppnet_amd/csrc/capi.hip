@@ -831,6 +831,59 @@ int ppn_gennet_stem_train_bwd(const void* dz, const float* x, const float* w, co
 int ppn_gennet_stem_train_tile(void) { return ppn::gennet_stem_tile(); }
 int ppn_gennet_stem_train_max_blocks(void) { return ppn::gennet_stem_max_blocks(); }
 
+// what the three tail-training entry points check alike: extents, the pixel count, the channel set, y's element count
+static int tail_train_sizes(int B, int H, int W, int C) {
+    if (B < 1 || H < 1 || W < 1 || C < 1) return PPN_E_INVALID;
+    if ((long long)B * H > 0x7fffffffLL || (long long)B * H * W > 0x7fffffffLL) return PPN_E_INVALID;     // overflow-safe in this order
+    if ((long long)B * H * W < 2) return PPN_E_INVALID;                       // one value per channel has no batch variance
+    if (!ppn::gennet_tail_channels_ok(C)) return PPN_E_UNSUPPORTED;           // C outside {8, 16, 24, 32}
+    if ((long long)B * H * W * C >= 0x80000000LL) return PPN_E_INVALID;       // y: 2^31 elements or more
+    return PPN_OK;
+}
+
+int64_t ppn_gennet_tail_train_workspace(int B, int H, int W, int C) {
+    if (tail_train_sizes(B, H, W, C) != PPN_OK) return -1;
+    return ppn::gennet_tail_train_workspace_bytes((long long)B * H * W, C);
+}
+
+int ppn_gennet_tail_train_fwd(const void* y, const float* gamma, const float* beta, const float* wf, const float* bf, void* out, float* stats,
+                              void* workspace, int B, int H, int W, int C, float eps, float negative_slope, int dtype, void* stream) {
+    if (!y || !gamma || !beta || !wf || !out || !stats || !workspace) return PPN_E_INVALID;              // bf may be NULL: no bias
+    if ((((uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)wf | (uintptr_t)out | (uintptr_t)workspace) & 15) != 0 ||
+        (((uintptr_t)bf | (uintptr_t)stats) & 3) != 0)
+        return PPN_E_INVALID;
+    if (dtype != 0 && dtype != 1) return PPN_E_INVALID;
+    if (!stem_scalar_ok(eps) || !stem_scalar_ok(negative_slope)) return PPN_E_INVALID;
+    const int ok = tail_train_sizes(B, H, W, C);
+    if (ok != PPN_OK) return ok;
+    const int e = ppn::gennet_tail_train_fwd_launch(y, gamma, beta, wf, bf, out, stats, workspace, B, H, W, C, eps, negative_slope, dtype,
+                                                    (hipStream_t)stream);
+    if (e == -1) return PPN_E_UNSUPPORTED;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_gennet_tail_train_bwd(const void* dout, const void* y, const float* gamma, const float* beta, const float* wf, const float* stats,
+                              void* workspace, void* dy, float* dgamma, float* dbeta, float* dwf, float* dbf, int B, int H, int W, int C,
+                              float negative_slope, int dtype, void* stream) {
+    if (!dout || !y || !gamma || !beta || !wf || !stats || !workspace || !dgamma || !dbeta || !dwf) return PPN_E_INVALID;   // dy, dbf may be NULL
+    if ((((uintptr_t)dout | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)wf | (uintptr_t)workspace | (uintptr_t)dy |
+          (uintptr_t)dgamma | (uintptr_t)dbeta | (uintptr_t)dwf) & 15) != 0 || (((uintptr_t)dbf | (uintptr_t)stats) & 3) != 0)
+        return PPN_E_INVALID;
+    if (dtype != 0 && dtype != 1) return PPN_E_INVALID;
+    if (!stem_scalar_ok(negative_slope)) return PPN_E_INVALID;
+    const int ok = tail_train_sizes(B, H, W, C);
+    if (ok != PPN_OK) return ok;
+    const int e = ppn::gennet_tail_train_bwd_launch(dout, y, gamma, beta, wf, stats, workspace, dy, dgamma, dbeta, dwf, dbf, B, H, W, C,
+                                                    negative_slope, dtype, (hipStream_t)stream);
+    if (e == -1) return PPN_E_UNSUPPORTED;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_gennet_tail_train_tile(void) { return ppn::gennet_tail_tile(); }
+int ppn_gennet_tail_train_max_blocks(void) { return ppn::gennet_tail_max_blocks(); }
+
 int ppn_upsample2x_nhwc(const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t relu, int32_t dtype,
                         void* stream) {
     return ppn_upsample2x_nhwc_bias(x, nullptr, y, B, H, W, C, relu, dtype, stream);

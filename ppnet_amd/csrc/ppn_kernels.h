@@ -156,6 +156,18 @@ int gennet_stem_train_bwd_launch(const void* dz, const float* x, const float* w,
                                  const float* stats, const double* moments, void* workspace, float* dw, float* dgamma, float* dbeta, int B, int H, int W,
                                  int C, float slope, int dtype, hipStream_t stream);
 
+// gennet_tail_train.hip: the training pair of GenNet's tail (BatchNorm2d on batch statistics + LeakyReLU + Conv2d(C, 1, 3, 1, 1)), C in
+// {8, 16, 24, 32}; the same conventions as the stem's.  bf, dbf and dy may be null (no bias; no input gradient wanted)
+int gennet_tail_channels_ok(int C);
+int gennet_tail_tile();
+int gennet_tail_max_blocks();
+long long gennet_tail_train_workspace_bytes(long long n, int C);
+int gennet_tail_train_fwd_launch(const void* y, const float* gamma, const float* beta, const float* wf, const float* bf, void* out, float* stats,
+                                 void* workspace, int B, int H, int W, int C, float eps, float slope, int dtype, hipStream_t stream);
+int gennet_tail_train_bwd_launch(const void* dout, const void* y, const float* gamma, const float* beta, const float* wf, const float* stats,
+                                 void* workspace, void* dy, float* dgamma, float* dbeta, float* dwf, float* dbf, int B, int H, int W, int C,
+                                 float slope, int dtype, hipStream_t stream);
+
 int resize_concat_launch(const void* const* x, const int* hw, const int* ch, int n, void* out, int B, int dtype, hipStream_t stream);
 int adaptive_pools_launch(const void* x, void* const* y, const int* scales, int n, int B, int H, int W, int C, int dtype, hipStream_t stream);
 int upsample2x_launch(const void* x, const void* bias, const void* add, void* y, int B, int H, int W, int C, int relu, int dtype, hipStream_t stream);

@@ -5,7 +5,8 @@ GenNet's AE-ViT, gennet._Attention, to the library's scaled_dot_product_attentio
 dim 8, PPNET_LIBRARY_LOSS sends the heads' training loss, heads.resized_decode_losses, to F.interpolate + F.cross_entropy instead of
 ppn_resize_ce_fwd / ppn_resize_ce_bwd, and PPNET_LIBRARY_EVAL sends the evaluation's area histograms, heads.resized_eval_areas, to
 F.interpolate + argmax + torch.bincount instead of ppn_seg_eval, and PPNET_LIBRARY_STEM sends the training stem of GenNet's AE-ViT,
-fused.stem_bn_act, to Conv2d + BatchNorm2d + LeakyReLU instead of ppn_gennet_stem_train_fwd / ppn_gennet_stem_train_bwd) — plus what every network file shares: stochastic depth, the "GPU inference" predicate, the image normalisation.  nat.py, swin.py, vit.py, heads.py and gennet.py import from here; none imports
+fused.stem_bn_act, to Conv2d + BatchNorm2d + LeakyReLU instead of ppn_gennet_stem_train_fwd / ppn_gennet_stem_train_bwd, and PPNET_LIBRARY_TAIL its training tail, fused.tail_bn_act_conv, to
+BatchNorm2d + LeakyReLU + Conv2d instead of ppn_gennet_tail_train_fwd / ppn_gennet_tail_train_bwd) — plus what every network file shares: stochastic depth, the "GPU inference" predicate, the image normalisation.  nat.py, swin.py, vit.py, heads.py and gennet.py import from here; none imports
 segnet.py, which re-exports these names under their earlier underscore spellings."""
 import os
 

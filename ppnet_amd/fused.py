@@ -9,7 +9,8 @@ attentions': neighbourhood (ppn_na2d_bwd, na.na2d_autograd), ViT's global one (p
 resize_cross_entropy below) — and the heads' bilinear up-sampling (ppn_upsample2x_nhwc_bwd, ppn_upsample2x_concat_nhwc_bwd,
 ppn_resize_concat_nhwc_bwd: upsample2x_nhwc, upsample2x_add, upsample2x_concat and resize_concat record their own kernels) — and
 GenNet's stem, convolution + BatchNorm on batch statistics + LeakyReLU (ppn_gennet_stem_train_fwd / ppn_gennet_stem_train_bwd,
-stem_bn_act at the end of this file)."""
+stem_bn_act near the end of this file) and its tail, BatchNorm on batch statistics + LeakyReLU + the 24 -> 1 convolution
+(ppn_gennet_tail_train_fwd / ppn_gennet_tail_train_bwd, tail_bn_act_conv at the end of this file)."""
 import ctypes
 import os
 
@@ -1728,3 +1729,134 @@ def stem_bn_act(x, conv, bn, negative_slope):
         bn.running_mean.mul_(1.0 - m).add_(stats[0], alpha=m)
         bn.running_var.mul_(1.0 - m).add_(stats[1], alpha=m * n / (n - 1))
     return z
+
+
+# ---------------------------------------------------------------------------------------------------------------- GenNet tail training
+TAIL_CALLS = {"fwd": 0, "bwd": 0}        # launches of ppn_gennet_tail_train_fwd / ppn_gennet_tail_train_bwd (like STEM_CALLS)
+TAIL_CHANNELS = frozenset({8, 16, 24, 32})                                  # csrc/gennet_tail_train.hip: the stem's set
+TAIL_THREADS = 256                       # work-items per workgroup of every kernel of csrc/gennet_tail_train.hip
+TAIL_LINE = 4                            # consecutive pixels per work-item: the unit of its vector loads and stores
+TAIL_TILE = 1024                         # pixels per workgroup tile (ppn_gennet_tail_train_tile)
+TAIL_MAX_BLOCKS = 512                    # workgroups at most in x of the summing kernels (ppn_gennet_tail_train_max_blocks)
+TAIL_SUMS = 11                           # float32 sums per channel of the backward: g, g xhat, z d(. - tap) for 9 taps
+TAIL_RECORD_MIN = 0                      # the smallest y.numel() that takes the kernels (no crossover was measured)
+
+
+def tail_train_workspace_bytes(B, H, W, C):
+    """ppn_gennet_tail_train_workspace's formula (include/ppnet_hip.h): per workgroup one [C][2] float64 partial forward, one [C][11] + 1
+    float32 partial backward, in the same buffer."""
+    return max(C * 2 * 8, (C * TAIL_SUMS + 1) * 4) * min(-(-(B * H * W) // TAIL_TILE), TAIL_MAX_BLOCKS)
+
+
+def library_tail():
+    """PPNET_LIBRARY_TAIL=1 (read at call time, like PPNET_LIBRARY_STEM): tail_bn_act_conv takes BatchNorm2d + LeakyReLU + Conv2d and the
+    framework's backwards instead of the HIP pair."""
+    return bool(os.environ.get("PPNET_LIBRARY_TAIL"))
+
+
+def tail_train_ok(y, bn, conv):
+    """Whether tail_bn_act_conv runs bn -> LeakyReLU -> conv on the HIP pair: y a contiguous CUDA [B,C,H,W], float32 or (under bfloat16
+    autocast, where the library composition takes it too) bfloat16, with B H W >= 2 (one value per channel is torch's own ValueError),
+    fewer than 2^31 elements and at least TAIL_RECORD_MIN; bn exactly a BatchNorm2d (a SyncBatchNorm reduces over ranks) in training mode,
+    affine, tracking running statistics with a float momentum, C features, C in TAIL_CHANNELS; conv exactly a Conv2d(C, 1, 3, 1, 1),
+    dilation 1, groups 1, zero padding; float32 parameters and buffers on y's device; autograd recording y or a parameter; no autocast or
+    bfloat16 autocast; and the knob off.  Everything else keeps the library."""
+    if library_tail() or not y.is_cuda or y.dtype not in (torch.float32, torch.bfloat16) or y.dim() != 4:
+        return False
+    if type(bn) is not torch.nn.BatchNorm2d or type(conv) is not torch.nn.Conv2d:
+        return False
+    B, C, H, W = y.shape
+    if (conv.in_channels != C or conv.out_channels != 1 or C not in TAIL_CHANNELS or conv.kernel_size != (3, 3) or conv.stride != (1, 1)
+            or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 or conv.padding_mode != "zeros"):
+        return False
+    if not (bn.training and bn.affine and bn.track_running_stats and isinstance(bn.momentum, float) and bn.num_features == C):
+        return False
+    if B * H * W < 2 or B * C * H * W >= 2 ** 31 or B * C * H * W < TAIL_RECORD_MIN or not y.is_contiguous():
+        return False
+    tensors = (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    if any(t is not None and (t.dtype != torch.float32 or t.device != y.device) for t in tensors) or bn.running_mean is None:
+        return False
+    autocast = torch.is_autocast_enabled("cuda")
+    if autocast and torch.get_autocast_dtype("cuda") != torch.bfloat16:
+        return False
+    if y.dtype == torch.bfloat16 and not autocast:                           # the library's convolution refuses bfloat16 z x float32 weight
+        return False
+    return recording(y, conv.weight, conv.bias, bn.weight, bn.bias)
+
+
+def _tail_workspace(B, H, W, C, dev):
+    need = L.lib.ppn_gennet_tail_train_workspace(B, H, W, C)
+    if need < 0:
+        raise L.PpnError(f"ppn_gennet_tail_train_workspace refuses B {B} H {H} W {W} C {C}", -1)
+    return torch.empty(max(need, 16) // 4, dtype=torch.float32, device=dev)
+
+
+def _tail_fwd(y, gamma, beta, wf, bf, eps, slope):
+    """ppn_gennet_tail_train_fwd on contiguous tensors (y [B,C,H,W] float32 or bfloat16; gamma, beta [C], wf [1,C,3,3] or [C,9], bf [1] or
+    None = no bias, float32): (out [B,1,H,W] of y's dtype, stats [3,C] float32)."""
+    B, C, H, W = y.shape
+    out = torch.empty(B, 1, H, W, dtype=y.dtype, device=y.device)
+    stats = torch.empty(3, C, dtype=torch.float32, device=y.device)
+    ws = _tail_workspace(B, H, W, C, y.device)
+    with torch.cuda.device(y.device):
+        rc = L.lib.ppn_gennet_tail_train_fwd(_p(y), _p(gamma), _p(beta), _p(wf), _p(bf), _p(out), _p(stats), _p(ws), B, H, W, C, float(eps),
+                                             float(slope), _DT[y.dtype], _stream(y))
+    L.check(rc, "ppn_gennet_tail_train_fwd")
+    TAIL_CALLS["fwd"] += 1
+    return out, stats
+
+
+def _tail_bwd(dout, y, gamma, beta, wf, stats, slope, need_dy=True, need_dbf=True):
+    """ppn_gennet_tail_train_bwd on contiguous tensors: (dy like y or None, dgamma [C], dbeta [C], dwf shaped like wf, dbf [1] or None)."""
+    B, C, H, W = y.shape
+    dy = torch.empty_like(y) if need_dy else None
+    dgamma, dbeta, dwf = torch.empty_like(gamma), torch.empty_like(beta), torch.empty_like(wf)
+    dbf = torch.empty(1, dtype=torch.float32, device=y.device) if need_dbf else None
+    ws = _tail_workspace(B, H, W, C, y.device)
+    with torch.cuda.device(y.device):
+        rc = L.lib.ppn_gennet_tail_train_bwd(_p(dout), _p(y), _p(gamma), _p(beta), _p(wf), _p(stats), _p(ws), _p(dy), _p(dgamma), _p(dbeta), _p(dwf),
+                                             _p(dbf), B, H, W, C, float(slope), _DT[y.dtype], _stream(y))
+    L.check(rc, "ppn_gennet_tail_train_bwd")
+    TAIL_CALLS["bwd"] += 1
+    return dy, dgamma, dbeta, dwf, dbf
+
+
+class _TailTrainFunction(torch.autograd.Function):
+    """(out, stats) = conv3x3_to_1(LeakyReLU(BatchNorm_train(y))) on ppn_gennet_tail_train_fwd / ppn_gennet_tail_train_bwd.  Saved: y, the
+    parameters and the statistics [3,C] — nothing else of y's size.  y gets dy, or None (and no second pass) when it needs no gradient."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, wf, bf, eps, slope):
+        gamma, beta, wf = gamma.detach().contiguous(), beta.detach().contiguous(), wf.detach().contiguous()
+        bf = bf.detach().contiguous() if bf is not None else None
+        out, stats = _tail_fwd(y, gamma, beta, wf, bf, eps, slope)
+        ctx.save_for_backward(y, gamma, beta, wf, stats)
+        ctx.slope, ctx.bias = slope, bf is not None
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout, _dstats):
+        y, gamma, beta, wf, stats = ctx.saved_tensors
+        dy, dgamma, dbeta, dwf, dbf = _tail_bwd(dout.to(y.dtype).contiguous(), y, gamma, beta, wf, stats, ctx.slope, ctx.needs_input_grad[0], ctx.bias)
+        return dy, dgamma, dbeta, dwf, dbf, None, None
+
+
+def tail_bn_act_conv(y, bn, negative_slope, conv):
+    """conv(leaky_relu(bn(y))) for GenNet's tail: the last decoder stage's BatchNorm2d and LeakyReLU and conv_final (C -> 1).  Where
+    tail_train_ok holds, the HIP pair: two reads of y forward, two reads of y and one write of dy backward, only y kept alive (DESIGN.md
+    section 28); out has the dtype the library composition gives (the autocast dtype under bfloat16 autocast, else y's); bn's running
+    statistics are updated as F.batch_norm does in training (momentum, the unbiased variance N / (N - 1)) and num_batches_tracked counts
+    the call.  Otherwise the library composition, untouched."""
+    if not tail_train_ok(y, bn, conv):
+        return conv(F.leaky_relu(bn(y), negative_slope))
+    out, stats = _TailTrainFunction.apply(y, bn.weight, bn.bias, conv.weight, conv.bias, bn.eps, float(negative_slope))
+    with torch.no_grad():
+        n, m = y.shape[0] * y.shape[2] * y.shape[3], bn.momentum
+        bn.num_batches_tracked.add_(1)
+        bn.running_mean.mul_(1.0 - m).add_(stats[0], alpha=m)
+        bn.running_var.mul_(1.0 - m).add_(stats[1], alpha=m * n / (n - 1))
+    if torch.is_autocast_enabled("cuda") and out.dtype != torch.get_autocast_dtype("cuda"):
+        out = out.to(torch.get_autocast_dtype("cuda"))                        # float32 y under autocast: the library's convolution rounds
+    return out

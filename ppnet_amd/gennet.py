@@ -282,8 +282,19 @@ class AEViT(nn.Module):
             wp, bp = last.s2_pack()
             wf, bf = self._final_pack()
             return fused.gennet_dec_final(x, wp, bp, last.slope, wf, bf)
-        for blk in self.dec_conv:
-            x = blk(x)
+        if isinstance(last, nn.Sequential) and len(last) == 3 and type(last[2]) is nn.LeakyReLU and self._final_f32 is None:
+            # the unprepared last stage, step by step: GPU training runs its BatchNorm (batch statistics) + LeakyReLU and conv_final as
+            # two reads of y and, backward, two reads of y and one write of dy (ppn_gennet_tail_train_fwd / ppn_gennet_tail_train_bwd;
+            # tail_from_sums below is the algebra).  PPNET_LIBRARY_TAIL (read at call time) keeps the three library ops.
+            for blk in self.dec_conv[:-1]:
+                x = blk(x)
+            y = last[0](x)
+            if fused.tail_train_ok(y, last[1], c):
+                return fused.tail_bn_act_conv(y, last[1], last[2].negative_slope, c)
+            x = last[2](last[1](y))
+        else:
+            for blk in self.dec_conv:
+                x = blk(x)
         if x.is_cuda and self._final_f32 is not None and c.out_channels == 1 and c.in_channels % 8 == 0 and c.in_channels <= 32:
             wf, bf = self._final_pack()                                      # dim -> 1 at full resolution: direct HIP kernel
             return fused.conv3x3_to1(x, wf, bf)
@@ -315,6 +326,38 @@ def stem_from_moments(x, dz, w, b, gamma, beta, eps, slope):
     X = rstd[:, None] * (w9 @ S2 + (b - mean)[:, None] * S1)                          # sum xhat p, from the moments
     dW = (gamma * rstd)[:, None] * (G - (dbeta / N)[:, None] * S1 - (dgamma / N)[:, None] * X)
     return z, mean, var, dW.reshape(w.shape), dgamma, dbeta
+
+
+def tail_from_sums(y, dout, gamma, beta, wf, bf, eps, slope):
+    """The algebra of the tail's training kernels (csrc/gennet_tail_train.hip) in torch ops, in the inputs' dtype, on
+    any device: out = conv3x3(leaky_relu(BatchNorm_train(y))) + bf with C -> 1 channels, and every gradient for an upstream dout.  The
+    batch statistics come from sum y and sum y^2; z is zero outside the image; everything that flows back through the one-channel
+    convolution is a 3 x 3 stencil of dout, so neither z nor its gradient is kept: 11 sums per channel (and sum dout), then dy.
+    y [B,C,H,W]; dout [B,1,H,W]; gamma, beta [C]; wf [1,C,3,3] or [C,9]; bf [1] or None.
+    Returns (out, mean, biased var, dy, dgamma, dbeta, dWf shaped like wf, dbf [1] or None)."""
+    B, C, H, W = y.shape
+    N = B * H * W
+    v = lambda t: t.reshape(1, C, 1, 1)
+    mean = y.sum((0, 2, 3)) / N
+    var = ((y * y).sum((0, 2, 3)) / N - mean * mean).clamp_min(0)
+    rstd = torch.rsqrt(var + eps)
+    xh = (y - v(mean)) * v(rstd)
+    u = v(gamma) * xh + v(beta)
+    z = torch.where(u > 0, u, u * slope)
+    w9 = wf.reshape(C, 9)
+    zp, dp = F.pad(z, (1, 1, 1, 1)), F.pad(dout, (1, 1, 1, 1))                            # zero outside the image, both
+    out = torch.zeros_like(dout) if bf is None else bf.reshape(1, 1, 1, 1).expand_as(dout).clone()
+    dz, dW = torch.zeros_like(y), torch.zeros_like(w9)
+    for t in range(9):
+        r, j = divmod(t, 3)
+        out += (zp[:, :, r:r + H, j:j + W] * v(w9[:, t])).sum(1, keepdim=True)          # z(p + tap)
+        ds = dp[:, :, 2 - r:2 - r + H, 2 - j:2 - j + W]                                   # d(q - tap), shared by all channels
+        dz += v(w9[:, t]) * ds
+        dW[:, t] = (z * ds).sum((0, 2, 3))
+    g = torch.where(u > 0, dz, dz * slope)
+    dbeta, dgamma = g.sum((0, 2, 3)), (g * xh).sum((0, 2, 3))                             # with dW: 11 sums per channel
+    dy = v(gamma * rstd) * (g - v(dbeta) / N - xh * v(dgamma) / N)
+    return out, mean, var, dy, dgamma, dbeta, dW.reshape(wf.shape), None if bf is None else dout.sum().reshape(1)
 
 
 AE = AEViT      # predict.py:12 `from networks import AEViT as AE`
