@@ -76,7 +76,8 @@ extern "C" {
  * ppn_patch_merge_ln_bwd, ppn_patch_merge_ln_rows and ppn_patch_merge_ln_max_blocks, and ppn_seg_tta, and ppn_gennet_stem_train_workspace,
  * ppn_gennet_stem_train_fwd, ppn_gennet_stem_train_bwd, ppn_gennet_stem_train_tile and ppn_gennet_stem_train_max_blocks, and
  * ppn_gennet_tail_train_workspace, ppn_gennet_tail_train_fwd, ppn_gennet_tail_train_bwd, ppn_gennet_tail_train_tile and
- * ppn_gennet_tail_train_max_blocks. */
+ * ppn_gennet_tail_train_max_blocks, and ppn_gennet_s2_tile, ppn_gennet_s2_max_blocks, ppn_gennet_s2_wgrad_workspace, ppn_gennet_s2_down,
+ * ppn_gennet_s2_up and ppn_gennet_s2_wgrad. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -695,6 +696,44 @@ int     ppn_gennet_tail_train_bwd(const void* dout, const void* y, const float* 
                                   void* workspace, void* dy /* may be NULL */, float* dgamma, float* dbeta, float* dwf,
                                   float* dbf /* may be NULL */,
                                   int B, int H, int W, int C, float negative_slope, int dtype, void* stream);
+
+/* The training kernels of GenNet's 24 -> 24 stride-2 stages (csrc/gennet_s2_train.hip; reference GenNet/networks/ae_vit.py, enc_conv's
+ * Conv2d(C, C, 3, 2, 1) and dec_conv's ConvTranspose2d(C, C, 3, 2, 1, output_padding=1)): one adjoint pair and one reduction serve both
+ * layer types, forward and backward, with the weights as the modules store them — nothing is flipped, transposed or repacked.
+ *
+ * H x W is always the BIG grid, the small one is Hs x Ws = ceil(H / 2) x ceil(W / 2); outside either grid everything is zero.
+ *   D, ppn_gennet_s2_down:  small[b,o,i,j] = bias[o] + sum_{c,ky,kx} w[o][c][ky][kx] big[b,c,2i+ky-1,2j+kx-1];  w is [out][in][3][3].
+ *   U, ppn_gennet_s2_up:    big[b,c,Y,X] = bias[c] + sum_{a,ky,kx : Y = 2i-1+ky, X = 2j-1+kx} w[a][c][ky][kx] small[b,a,i,j];  w is
+ *      [in][out][3][3]; gather form (even Y takes ky = 1, odd Y takes ky = 0 and ky = 2, X alike): one writer per element.  Each axis of
+ *      the big extent is 2 Hs or 2 Hs - 1, as passed.
+ *   W, ppn_gennet_s2_wgrad: dw[a][c][ky][kx] = sum_{b,i,j} small[b,a,i,j] big[b,c,2i+ky-1,2j+kx-1], [small channel][big channel][3][3];
+ *      sum_small[a] = sum_{b,i,j} small[b,a,i,j] and sum_big[c] = sum_{b,Y,X} big[b,c,Y,X] in the same pass (either may be NULL).
+ * Conv2d (weight [co][ci]): forward D(x, w) + bias; input gradient U(dy, w) at x's extent; weight gradient W(small = dy, big = x), bias
+ * gradient sum_small.  ConvTranspose2d (weight [ci][co]): forward U(x, w) + bias at 2H x 2W; input gradient D(dy, w); weight gradient
+ * W(small = x, big = dy), bias gradient sum_big.
+ *
+ * big [B][C][H][W] and small [B][C][Hs][Ws] contiguous NCHW of `dtype` (0 = float32, 1 = bfloat16); w [C][C][3][3], bias [C], dw, sum_small
+ * and sum_big float32.  Products and sums are float32 FMAs in both data types (bfloat16 is only the widening on load and the one rounding
+ * on store).  W keeps one float32 partial [C C 9 + 2 C] per workgroup in `workspace`; a finishing kernel adds the partials in a fixed
+ * order in float64 and rounds once.  No atomics anywhere: two calls give the same bits.
+ * ppn_gennet_s2_wgrad_workspace(B, Hs, Ws) — of the SMALL grid: the bytes `workspace` holds,
+ *   (24 * 24 * 9 + 2 * 24) * 4 * min(ceil(B Hs Ws / ppn_gennet_s2_tile()), ppn_gennet_s2_max_blocks()); < 0 for sizes the entry refuses.
+ * ppn_gennet_s2_tile(): the small pixels of one workgroup tile (512).  ppn_gennet_s2_max_blocks(): the most workgroups of W; past that
+ * many tiles a workgroup strides.
+ *
+ * C = 24 only.  Before any HIP call: PPN_E_INVALID for a NULL required pointer, a tensor, weight or workspace pointer that is not 16-byte
+ * aligned (bias, sum_small, sum_big: 4), an extent below 1, a dtype outside {0, 1}, 2^31 elements and more in big; PPN_E_UNSUPPORTED for
+ * another C. */
+int     ppn_gennet_s2_tile(void);
+int     ppn_gennet_s2_max_blocks(void);
+int64_t ppn_gennet_s2_wgrad_workspace(int B, int Hs, int Ws);            /* bytes; < 0 for sizes the entry refuses */
+int     ppn_gennet_s2_down (const void* big, const float* w, const float* bias /* may be NULL */, void* small,
+                            int B, int H, int W, int C, int dtype, void* stream);
+int     ppn_gennet_s2_up   (const void* small, const float* w, const float* bias /* may be NULL */, void* big,
+                            int B, int H, int W, int C, int dtype, void* stream);          /* H, W: the BIG extent */
+int     ppn_gennet_s2_wgrad(const void* small, const void* big, void* workspace, float* dw,
+                            float* sum_small /* may be NULL */, float* sum_big /* may be NULL */,
+                            int B, int H, int W, int C, int dtype, void* stream);
 
 /* Bilinear x2 up-sampling of an NHWC tensor x [B][H][W][C] -> y [B][2H][2W][C] with PyTorch's
  * F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) arithmetic (the SETR-UP head's Upsample,

@@ -72,7 +72,9 @@ EXPORTS = ("ppn_version", "ppn_error_string", "ppn_last_hip_error", "ppn_polyfit
            "ppn_gennet_stem_train_workspace", "ppn_gennet_stem_train_fwd", "ppn_gennet_stem_train_bwd", "ppn_gennet_stem_train_tile",
            "ppn_gennet_stem_train_max_blocks",
            "ppn_gennet_tail_train_workspace", "ppn_gennet_tail_train_fwd", "ppn_gennet_tail_train_bwd", "ppn_gennet_tail_train_tile",
-           "ppn_gennet_tail_train_max_blocks")
+           "ppn_gennet_tail_train_max_blocks",
+           "ppn_gennet_s2_tile", "ppn_gennet_s2_max_blocks", "ppn_gennet_s2_wgrad_workspace", "ppn_gennet_s2_down", "ppn_gennet_s2_up",
+           "ppn_gennet_s2_wgrad")
 
 
 def _load():
@@ -172,6 +174,13 @@ def _load():
     lib.ppn_gennet_tail_train_bwd.argtypes = [_p] * 12 + [C.c_int] * 4 + [C.c_float, C.c_int, _p]
     lib.ppn_gennet_tail_train_tile.argtypes = []
     lib.ppn_gennet_tail_train_max_blocks.argtypes = []
+    lib.ppn_gennet_s2_tile.argtypes = []
+    lib.ppn_gennet_s2_max_blocks.argtypes = []
+    lib.ppn_gennet_s2_wgrad_workspace.argtypes = [C.c_int] * 3
+    lib.ppn_gennet_s2_wgrad_workspace.restype = C.c_int64
+    lib.ppn_gennet_s2_down.argtypes = [_p] * 4 + [C.c_int] * 5 + [_p]
+    lib.ppn_gennet_s2_up.argtypes = [_p] * 4 + [C.c_int] * 5 + [_p]
+    lib.ppn_gennet_s2_wgrad.argtypes = [_p] * 6 + [C.c_int] * 5 + [_p]
     lib.ppn_grid_to_image.argtypes = [_p, _p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, _p]
     lib.ppn_seg_labels_2class.argtypes = [_p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
     lib.ppn_bias_act_nhwc.argtypes = [_p, _p, C.c_int64, C.c_int32, C.c_float, C.c_int32, _p]
@@ -223,7 +232,8 @@ def _load():
         getattr(lib, name)
         if name not in ("ppn_error_string", "ppn_na2d_bwd_workspace", "ppn_na2d_bwd_vpad_workspace", "ppn_mhsa_bwd_workspace", "ppn_swin_wmsa_bwd_workspace",
                         "ppn_resize_ce_workspace", "ppn_ohem_ce_workspace", "ppn_resize_dice_workspace", "ppn_residual_layernorm_bwd_workspace",
-                        "ppn_patch_merge_ln_bwd_workspace", "ppn_gennet_stem_train_workspace", "ppn_gennet_tail_train_workspace"):
+                        "ppn_patch_merge_ln_bwd_workspace", "ppn_gennet_stem_train_workspace", "ppn_gennet_tail_train_workspace",
+                        "ppn_gennet_s2_wgrad_workspace"):
             getattr(lib, name).restype = C.c_int
     return lib
 

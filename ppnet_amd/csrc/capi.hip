@@ -884,6 +884,62 @@ int ppn_gennet_tail_train_bwd(const void* dout, const void* y, const float* gamm
 int ppn_gennet_tail_train_tile(void) { return ppn::gennet_tail_tile(); }
 int ppn_gennet_tail_train_max_blocks(void) { return ppn::gennet_tail_max_blocks(); }
 
+// what the stride-2 entry points check alike: extents, the width, the big tensor's element count (H, W: the big extent)
+static int s2_sizes(int B, int H, int W, int C, int dtype) {
+    if (dtype != 0 && dtype != 1) return PPN_E_INVALID;
+    if (B < 1 || H < 1 || W < 1 || C < 1) return PPN_E_INVALID;
+    if (C != 24) return PPN_E_UNSUPPORTED;
+    if ((long long)B * H > 0x7fffffffLL || (long long)B * H * W > 0x7fffffffLL) return PPN_E_INVALID;     // overflow-safe in this order
+    if ((long long)B * H * W * C >= 0x80000000LL) return PPN_E_INVALID;       // the big tensor: 2^31 elements or more
+    return PPN_OK;
+}
+
+int ppn_gennet_s2_tile(void) { return ppn::gennet_s2_tile(); }
+int ppn_gennet_s2_max_blocks(void) { return ppn::gennet_s2_max_blocks(); }
+
+int64_t ppn_gennet_s2_wgrad_workspace(int B, int Hs, int Ws) {
+    if (B < 1 || Hs < 1 || Ws < 1) return -1;
+    if ((long long)B * Hs > 0x7fffffffLL || (long long)B * Hs * Ws > 0x7fffffffLL) return -1;
+    if ((long long)B * Hs * Ws * 24 >= 0x80000000LL) return -1;               // the small tensor alone is past what the entry takes
+    return ppn::gennet_s2_wgrad_workspace_bytes((long long)B * Hs * Ws);
+}
+
+int ppn_gennet_s2_down(const void* big, const float* w, const float* bias, void* small, int B, int H, int W, int C, int dtype, void* stream) {
+    if (!big || !w || !small) return PPN_E_INVALID;                           // bias may be NULL: none
+    if ((((uintptr_t)big | (uintptr_t)w | (uintptr_t)small) & 15) != 0 || ((uintptr_t)bias & 3) != 0) return PPN_E_INVALID;
+    const int ok = s2_sizes(B, H, W, C, dtype);
+    if (ok != PPN_OK) return ok;
+    const int e = ppn::gennet_s2_down_launch(big, w, bias, small, B, H, W, C, dtype, (hipStream_t)stream);
+    if (e == -1) return PPN_E_UNSUPPORTED;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_gennet_s2_up(const void* small, const float* w, const float* bias, void* big, int B, int H, int W, int C, int dtype, void* stream) {
+    if (!small || !w || !big) return PPN_E_INVALID;                           // bias may be NULL: none
+    if ((((uintptr_t)small | (uintptr_t)w | (uintptr_t)big) & 15) != 0 || ((uintptr_t)bias & 3) != 0) return PPN_E_INVALID;
+    const int ok = s2_sizes(B, H, W, C, dtype);
+    if (ok != PPN_OK) return ok;
+    const int e = ppn::gennet_s2_up_launch(small, w, bias, big, B, H, W, C, dtype, (hipStream_t)stream);
+    if (e == -1) return PPN_E_UNSUPPORTED;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
+int ppn_gennet_s2_wgrad(const void* small, const void* big, void* workspace, float* dw, float* sum_small, float* sum_big, int B, int H, int W,
+                        int C, int dtype, void* stream) {
+    if (!small || !big || !workspace || !dw) return PPN_E_INVALID;            // sum_small, sum_big may be NULL: not wanted
+    if ((((uintptr_t)small | (uintptr_t)big | (uintptr_t)workspace | (uintptr_t)dw) & 15) != 0 ||
+        (((uintptr_t)sum_small | (uintptr_t)sum_big) & 3) != 0)
+        return PPN_E_INVALID;
+    const int ok = s2_sizes(B, H, W, C, dtype);
+    if (ok != PPN_OK) return ok;
+    const int e = ppn::gennet_s2_wgrad_launch(small, big, workspace, dw, sum_small, sum_big, B, H, W, C, dtype, (hipStream_t)stream);
+    if (e == -1) return PPN_E_UNSUPPORTED;
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int ppn_upsample2x_nhwc(const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t relu, int32_t dtype,
                         void* stream) {
     return ppn_upsample2x_nhwc_bias(x, nullptr, y, B, H, W, C, relu, dtype, stream);

@@ -168,6 +168,17 @@ int gennet_tail_train_bwd_launch(const void* dout, const void* y, const float* g
                                  void* workspace, void* dy, float* dgamma, float* dbeta, float* dwf, float* dbf, int B, int H, int W, int C,
                                  float slope, int dtype, hipStream_t stream);
 
+// gennet_s2_train.hip: the training kernels of GenNet's 24 -> 24 stride-2 stages — D (big -> small), U (small -> big, gather form) and W
+// (the weight gradient and both channel sums) on contiguous NCHW float32 / bfloat16 with the weights as stored; H, W: the big extent,
+// the small one ceil(H / 2) x ceil(W / 2); ns = B Hs Ws.  bias, sum_small and sum_big may be null.  -1: C is not 24
+int gennet_s2_tile();
+int gennet_s2_max_blocks();
+long long gennet_s2_wgrad_workspace_bytes(long long ns);
+int gennet_s2_down_launch(const void* big, const float* w, const float* bias, void* small, int B, int H, int W, int C, int dtype, hipStream_t stream);
+int gennet_s2_up_launch(const void* small, const float* w, const float* bias, void* big, int B, int H, int W, int C, int dtype, hipStream_t stream);
+int gennet_s2_wgrad_launch(const void* small, const void* big, void* workspace, float* dw, float* sum_small, float* sum_big, int B, int H, int W,
+                           int C, int dtype, hipStream_t stream);
+
 int resize_concat_launch(const void* const* x, const int* hw, const int* ch, int n, void* out, int B, int dtype, hipStream_t stream);
 int adaptive_pools_launch(const void* x, void* const* y, const int* scales, int n, int B, int H, int W, int C, int dtype, hipStream_t stream);
 int upsample2x_launch(const void* x, const void* bias, const void* add, void* y, int B, int H, int W, int C, int relu, int dtype, hipStream_t stream);

@@ -10,7 +10,8 @@ resize_cross_entropy below) — and the heads' bilinear up-sampling (ppn_upsampl
 ppn_resize_concat_nhwc_bwd: upsample2x_nhwc, upsample2x_add, upsample2x_concat and resize_concat record their own kernels) — and
 GenNet's stem, convolution + BatchNorm on batch statistics + LeakyReLU (ppn_gennet_stem_train_fwd / ppn_gennet_stem_train_bwd,
 stem_bn_act near the end of this file) and its tail, BatchNorm on batch statistics + LeakyReLU + the 24 -> 1 convolution
-(ppn_gennet_tail_train_fwd / ppn_gennet_tail_train_bwd, tail_bn_act_conv at the end of this file)."""
+(ppn_gennet_tail_train_fwd / ppn_gennet_tail_train_bwd, tail_bn_act_conv near the end of this file) and its six 24 -> 24 stride-2
+stages' convolutions (ppn_gennet_s2_down / ppn_gennet_s2_up / ppn_gennet_s2_wgrad, conv_s2 at the end of this file)."""
 import ctypes
 import os
 
@@ -1860,3 +1861,157 @@ def tail_bn_act_conv(y, bn, negative_slope, conv):
     if torch.is_autocast_enabled("cuda") and out.dtype != torch.get_autocast_dtype("cuda"):
         out = out.to(torch.get_autocast_dtype("cuda"))                        # float32 y under autocast: the library's convolution rounds
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- GenNet stride-2 stage training
+S2_CALLS = {"down": 0, "up": 0, "wgrad": 0}    # launches of ppn_gennet_s2_down / ppn_gennet_s2_up / ppn_gennet_s2_wgrad (like TAIL_CALLS)
+S2_CHANNELS = 24                         # csrc/gennet_s2_train.hip: the one width
+S2_TILE = 512                            # small pixels per workgroup tile (ppn_gennet_s2_tile)
+S2_MAX_BLOCKS = 768                      # workgroups at most of the weight-gradient kernel (ppn_gennet_s2_max_blocks)
+S2_RECORD_MIN = 8 * 24 * 224 * 224       # the smallest big-side numel() that takes the kernels: the smallest measured size at which a
+#                                          stage still wins; below it the launches cost more than the library's
+S2_DTYPES = frozenset({torch.float32})   # the kernels' data types that take them: the bfloat16 step did not beat the parent's by more
+#                                          than the spread when it was measured, so bfloat16 autocast keeps the library
+
+
+def s2_wgrad_workspace_bytes(B, Hs, Ws):
+    """ppn_gennet_s2_wgrad_workspace's formula (include/ppnet_hip.h), of the SMALL grid: per workgroup one float32 partial of the
+    24 * 24 * 9 weight-gradient sums and the 2 * 24 channel sums."""
+    return (S2_CHANNELS * S2_CHANNELS * 9 + 2 * S2_CHANNELS) * 4 * min(-(-(B * Hs * Ws) // S2_TILE), S2_MAX_BLOCKS)
+
+
+def library_s2():
+    """PPNET_LIBRARY_S2=1 (read at call time, like PPNET_LIBRARY_TAIL): conv_s2 takes the library's Conv2d / ConvTranspose2d and the
+    framework's backwards instead of the HIP kernels."""
+    return bool(os.environ.get("PPNET_LIBRARY_S2"))
+
+
+def module_hooked(mod):
+    """Whether a forward or backward hook is registered on `mod` (or on every module): such a module is run through its own __call__."""
+    from torch.nn.modules import module as M
+    return bool(mod._forward_hooks or mod._forward_pre_hooks or mod._backward_hooks or mod._backward_pre_hooks or M._global_forward_hooks
+                or M._global_forward_pre_hooks or M._global_backward_hooks or M._global_backward_pre_hooks)
+
+
+def conv_s2_ok(x, conv):
+    """Whether conv_s2 runs conv on the HIP kernels: x a contiguous CUDA [B,24,H,W], float32 or (under bfloat16 autocast only, where the
+    library takes it too) bfloat16; conv exactly a Conv2d(24, 24, 3, 2, 1) or a ConvTranspose2d(24, 24, 3, 2, 1, output_padding=1),
+    dilation 1, groups 1, zero padding; float32 parameters on x's device; fewer than 2^31 elements on both sides and at least
+    S2_RECORD_MIN on the big one; the kernels' data type (bfloat16 under autocast) in S2_DTYPES; autograd recording x or a parameter;
+    no autocast or bfloat16 autocast; no hook on conv; and the knob off.  Everything else keeps the library."""
+    if library_s2() or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16) or x.dim() != 4:
+        return False
+    if module_hooked(conv):                                                  # a hook watches conv's own call: it keeps it
+        return False
+    up = type(conv) is torch.nn.ConvTranspose2d
+    if not up and type(conv) is not torch.nn.Conv2d:
+        return False
+    B, C, H, W = x.shape
+    if (C != S2_CHANNELS or conv.in_channels != C or conv.out_channels != C or conv.kernel_size != (3, 3) or conv.stride != (2, 2)
+            or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 or conv.padding_mode != "zeros"
+            or (up and conv.output_padding != (1, 1))):
+        return False
+    big = B * C * H * W * (4 if up else 1)
+    if B * H * W < 1 or big >= 2 ** 31 or big < S2_RECORD_MIN or not x.is_contiguous():
+        return False
+    if any(t is not None and (t.dtype != torch.float32 or t.device != x.device) for t in (conv.weight, conv.bias)):
+        return False
+    autocast = torch.is_autocast_enabled("cuda")
+    if autocast and torch.get_autocast_dtype("cuda") != torch.bfloat16:
+        return False
+    if x.dtype == torch.bfloat16 and not autocast:                           # the library's convolution refuses bfloat16 x x float32 weight
+        return False
+    if (torch.bfloat16 if autocast else x.dtype) not in S2_DTYPES:            # the data type the kernels would run in
+        return False
+    return recording(x, conv.weight, conv.bias)
+
+
+def _s2_down(big, w, bias):
+    """ppn_gennet_s2_down on contiguous tensors (big [B,24,H,W] float32 or bfloat16; w [24,24,3,3] read as [out][in], bias [24] or None,
+    float32): small [B,24,ceil(H/2),ceil(W/2)] of big's dtype."""
+    B, C, H, W = big.shape
+    small = torch.empty(B, C, (H + 1) // 2, (W + 1) // 2, dtype=big.dtype, device=big.device)
+    with torch.cuda.device(big.device):
+        rc = L.lib.ppn_gennet_s2_down(_p(big), _p(w), _p(bias), _p(small), B, H, W, C, _DT[big.dtype], _stream(big))
+    L.check(rc, "ppn_gennet_s2_down")
+    S2_CALLS["down"] += 1
+    return small
+
+
+def _s2_up(small, w, bias, H, W):
+    """ppn_gennet_s2_up on contiguous tensors (small [B,24,ceil(H/2),ceil(W/2)]; w [24,24,3,3] read as [in][out]): big [B,24,H,W]."""
+    B, C, Hs, Ws = small.shape
+    if (H + 1) // 2 != Hs or (W + 1) // 2 != Ws:
+        raise ValueError(f"_s2_up: the extent {H} x {W} does not halve to {Hs} x {Ws}")
+    big = torch.empty(B, C, H, W, dtype=small.dtype, device=small.device)
+    with torch.cuda.device(small.device):
+        rc = L.lib.ppn_gennet_s2_up(_p(small), _p(w), _p(bias), _p(big), B, H, W, C, _DT[small.dtype], _stream(small))
+    L.check(rc, "ppn_gennet_s2_up")
+    S2_CALLS["up"] += 1
+    return big
+
+
+def _s2_wgrad(small, big, want_small=True, want_big=True):
+    """ppn_gennet_s2_wgrad on contiguous tensors of one dtype: (dw [24,24,3,3] as [small channel][big channel], sum_small [24] or None,
+    sum_big [24] or None), float32."""
+    B, C, H, W = big.shape
+    Hs, Ws = small.shape[2], small.shape[3]
+    if small.shape[:2] != big.shape[:2] or (H + 1) // 2 != Hs or (W + 1) // 2 != Ws or small.dtype != big.dtype:
+        raise ValueError(f"_s2_wgrad: small {tuple(small.shape)} {small.dtype} does not belong to big {tuple(big.shape)} {big.dtype}")
+    need = L.lib.ppn_gennet_s2_wgrad_workspace(B, Hs, Ws)
+    if need < 0:
+        raise L.PpnError(f"ppn_gennet_s2_wgrad_workspace refuses B {B} Hs {Hs} Ws {Ws}", -1)
+    ws = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=big.device)
+    dw = torch.empty(C, C, 3, 3, dtype=torch.float32, device=big.device)
+    ssum = torch.empty(C, dtype=torch.float32, device=big.device) if want_small else None
+    bsum = torch.empty(C, dtype=torch.float32, device=big.device) if want_big else None
+    with torch.cuda.device(big.device):
+        rc = L.lib.ppn_gennet_s2_wgrad(_p(small), _p(big), _p(ws), _p(dw), _p(ssum), _p(bsum), B, H, W, C, _DT[big.dtype], _stream(big))
+    L.check(rc, "ppn_gennet_s2_wgrad")
+    S2_CALLS["wgrad"] += 1
+    return dw, ssum, bsum
+
+
+class _ConvS2Function(torch.autograd.Function):
+    """conv(x) for the two 24 -> 24 stride-2 layer types on ppn_gennet_s2_down / ppn_gennet_s2_up / ppn_gennet_s2_wgrad (the table in
+    include/ppnet_hip.h).  `dtype` is the one the kernels run in: x's, or bfloat16 for a float32 x under bfloat16 autocast.  Saved: x in
+    that dtype and the weight.  dx comes back in x's own dtype, or None (and no kernel) when x needs no gradient; the bias always gets
+    its gradient — a plain channel sum of dy from the weight-gradient pass — because DistributedDataParallel waits for every parameter."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, up, dtype):
+        w = w.detach().contiguous()
+        b = b.detach().contiguous() if b is not None else None
+        xk = x.to(dtype).contiguous()
+        y = _s2_up(xk, w, b, 2 * x.shape[2], 2 * x.shape[3]) if up else _s2_down(xk, w, b)
+        ctx.save_for_backward(xk, w)
+        ctx.up, ctx.bias, ctx.x_dtype = up, b is not None, x.dtype
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        xk, w = ctx.saved_tensors
+        dy = dy.to(xk.dtype).contiguous()
+        dx = None
+        if ctx.up:                                                           # ConvTranspose2d: x is the small side
+            if ctx.needs_input_grad[0]:
+                dx = _s2_down(dy, w, None)
+            dw, _, db = _s2_wgrad(xk, dy, False, ctx.bias)
+        else:                                                                # Conv2d: x is the big side
+            if ctx.needs_input_grad[0]:
+                dx = _s2_up(dy, w, None, xk.shape[2], xk.shape[3])
+            dw, db, _ = _s2_wgrad(dy, xk, ctx.bias, False)
+        if dx is not None and dx.dtype != ctx.x_dtype:
+            dx = dx.to(ctx.x_dtype)
+        return dx, dw, db, None, None
+
+
+def conv_s2(x, conv):
+    """conv(x) for GenNet's six 24 -> 24 stride-2 stages.  Where conv_s2_ok holds, the HIP kernels, forward and backward (DESIGN.md section
+    29); under bfloat16 autocast a float32 x (the first decoder stage's input, from the trunk's residual stream) is cast to bfloat16
+    first and the output is bfloat16, as the library gives.  Otherwise the library's conv(x), untouched."""
+    if not conv_s2_ok(x, conv):
+        return conv(x)
+    dtype = torch.bfloat16 if torch.is_autocast_enabled("cuda") else x.dtype
+    return _ConvS2Function.apply(x, conv.weight, conv.bias, type(conv) is torch.nn.ConvTranspose2d, dtype)

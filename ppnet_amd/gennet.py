@@ -183,6 +183,16 @@ class _FusedStage(nn.Module):
         return fused.bias_act_(y.contiguous(memory_format=torch.channels_last), c.bias, self.slope)
 
 
+def _run_stage(blk, x):
+    """One enc_conv / dec_conv stage.  An unprepared stage (conv, BatchNorm2d, LeakyReLU) runs its convolution through fused.conv_s2: GPU
+    training of the 24 -> 24 stride-2 stages takes the HIP kernels forward and backward (ppn_gennet_s2_down / ppn_gennet_s2_up /
+    ppn_gennet_s2_wgrad; s2_from_adjoint below is the algebra), everything else the library's conv(x), untouched.  PPNET_LIBRARY_S2
+    (read at call time) keeps the library.  BatchNorm and LeakyReLU stay library ops."""
+    if type(blk) is nn.Sequential and len(blk) == 3 and not fused.module_hooked(blk):     # a hooked stage keeps its own call
+        return blk[2](blk[1](fused.conv_s2(x, blk[0])))
+    return blk(x)
+
+
 def _ln(x, ln):
     # The CPU branches of this module (here and in _FusedStage) are not a product fallback: they let the CPU golden test
     # (tests/test_gennet_golden.py) check the module's wiring against the reference's own outputs without a GPU.  PPNet, the
@@ -260,7 +270,7 @@ class AEViT(nn.Module):
             else:
                 x = cf(x)
             for blk in self.enc_conv:
-                x = blk(x)
+                x = _run_stage(blk, x)
         B, C, H, W = x.shape
         if (x.is_cuda and x.dtype == torch.bfloat16 and self._final_f32 is not None and C == 24 and H * W <= 1024 and (H * W) % 8 == 0
                 and self.vit_blocks[0].attn.num_heads == 3 and not os.environ.get("PPNET_LIBRARY_TRUNK")):
@@ -287,8 +297,8 @@ class AEViT(nn.Module):
             # two reads of y and, backward, two reads of y and one write of dy (ppn_gennet_tail_train_fwd / ppn_gennet_tail_train_bwd;
             # tail_from_sums below is the algebra).  PPNET_LIBRARY_TAIL (read at call time) keeps the three library ops.
             for blk in self.dec_conv[:-1]:
-                x = blk(x)
-            y = last[0](x)
+                x = _run_stage(blk, x)
+            y = fused.conv_s2(x, last[0])
             if fused.tail_train_ok(y, last[1], c):
                 return fused.tail_bn_act_conv(y, last[1], last[2].negative_slope, c)
             x = last[2](last[1](y))
@@ -358,6 +368,39 @@ def tail_from_sums(y, dout, gamma, beta, wf, bf, eps, slope):
     dbeta, dgamma = g.sum((0, 2, 3)), (g * xh).sum((0, 2, 3))                             # with dW: 11 sums per channel
     dy = v(gamma * rstd) * (g - v(dbeta) / N - xh * v(dgamma) / N)
     return out, mean, var, dy, dgamma, dbeta, dW.reshape(wf.shape), None if bf is None else dout.sum().reshape(1)
+
+
+def s2_from_adjoint(x, dy, weight, transposed):
+    """The algebra of the stride-2 stages' training kernels (csrc/gennet_s2_train.hip) in torch ops, in the inputs'
+    dtype, on any device: one adjoint pair D (big -> small) / U (small -> big) and one reduction W serve Conv2d(C, C, 3, 2, 1) and
+    ConvTranspose2d(C, C, 3, 2, 1, output_padding=1) with the weight as stored, built from strided slices and einsum.
+    x [B,C,H,W]; dy shaped like the layer's output; weight [C,C,3,3] ([out][in] for Conv2d, [in][out] transposed).
+    Returns (forward without bias, dx, dw in the stored layout, dbias)."""
+    def taps(big, Hs, Ws):                                                   # tap (ky, kx) -> big(2i + ky - 1, 2j + kx - 1), zero outside
+        H, W = big.shape[2], big.shape[3]
+        bp = F.pad(big, (1, 2 * Ws - W, 1, 2 * Hs - H))
+        return [[bp[:, :, ky:ky + 2 * Hs:2, kx:kx + 2 * Ws:2] for kx in range(3)] for ky in range(3)]
+
+    def down(big, w):                                                        # D: w [out][in]
+        Hs, Ws = (big.shape[2] + 1) // 2, (big.shape[3] + 1) // 2
+        t = taps(big, Hs, Ws)
+        return sum(torch.einsum("oc,bcij->boij", w[:, :, ky, kx], t[ky][kx]) for ky in range(3) for kx in range(3))
+
+    def up(small, w, H, W):                                                  # U: w [in][out], scattered through D's own index map
+        B, _, Hs, Ws = small.shape
+        op = torch.zeros(B, w.shape[1], 2 * Hs + 1, 2 * Ws + 1, dtype=small.dtype, device=small.device)
+        for ky in range(3):
+            for kx in range(3):
+                op[:, :, ky:ky + 2 * Hs:2, kx:kx + 2 * Ws:2] += torch.einsum("ac,baij->bcij", w[:, :, ky, kx], small)
+        return op[:, :, 1:1 + H, 1:1 + W]
+
+    def wgrad(small, big):                                                   # W: [small channel][big channel][3][3]
+        t = taps(big, small.shape[2], small.shape[3])
+        return torch.stack([torch.stack([torch.einsum("baij,bcij->ac", small, t[ky][kx]) for kx in range(3)], -1) for ky in range(3)], -2)
+
+    if transposed:
+        return up(x, weight, 2 * x.shape[2], 2 * x.shape[3]), down(dy, weight), wgrad(x, dy), dy.sum((0, 2, 3))
+    return down(x, weight), up(dy, weight, x.shape[2], x.shape[3]), wgrad(dy, x), dy.sum((0, 2, 3))
 
 
 AE = AEViT      # predict.py:12 `from networks import AEViT as AE`
