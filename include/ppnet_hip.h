@@ -77,7 +77,7 @@ extern "C" {
  * ppn_gennet_stem_train_fwd, ppn_gennet_stem_train_bwd, ppn_gennet_stem_train_tile and ppn_gennet_stem_train_max_blocks, and
  * ppn_gennet_tail_train_workspace, ppn_gennet_tail_train_fwd, ppn_gennet_tail_train_bwd, ppn_gennet_tail_train_tile and
  * ppn_gennet_tail_train_max_blocks, and ppn_gennet_s2_tile, ppn_gennet_s2_max_blocks, ppn_gennet_s2_wgrad_workspace, ppn_gennet_s2_down,
- * ppn_gennet_s2_up and ppn_gennet_s2_wgrad. */
+ * ppn_gennet_s2_up and ppn_gennet_s2_wgrad, and ppn_wmsa_fwd. */
 #define PPN_ABI_VERSION 111
 int         ppn_version(void);
 const char* ppn_error_string(int code);
@@ -294,6 +294,23 @@ int ppn_na2d_fwd_vpad(const void* qkv, const void* pad_kv, const float* rpb, voi
  * dtype 0 = float32, 1 = bfloat16 (float32 accumulation, matrix cores). */
 int ppn_swin_wmsa_fwd(const void* qkv, const void* pad_kv, const float* rpb, void* out, int32_t B, int32_t H, int32_t W,
                       int32_t heads, int32_t window, int32_t shift, float scale, int32_t dtype, void* stream);
+
+/* The same forward generalised over (window w, head dim d), for GenNet's AESwin (GenNet/networks/vanilla_swin.py:239-284,325-376,
+ * 429-454 between the qkv and the proj Linear; csrc/wmsa_gen.hip).  qkv [B][H][W][3][heads][d], real tokens only; pad_kv
+ * [3][heads][d] the k / v of every padded position; rpb [heads][2w-1][2w-1] float32 = the relative_position_bias_table
+ * [(2w-1)^2][heads] transposed, indexed [h][dy + w-1][dx + w-1] with (dy, dx) = query minus key inside the window; out
+ * [B][H][W][heads*d], only real tokens written.  The grid is padded to Hp = ceil(H/w)*w, Wp likewise (also when H or W < w);
+ * window (wy, wx) slot (i, j) holds padded position ((w wy + i + shift) mod Hp, (w wx + j + shift) mod Wp).  With shift > 0, slots
+ * of different regions (per axis of the shifted frame: y < Hp-w, Hp-w <= y < Hp-shift, the rest) get -100 added to the logit (not
+ * -inf) - also when one window covers the whole grid (a 14 x 14 grid under w = 14, shift 7 is one window with four regions).
+ * Logit = (q * scale) . k + bias.  (w, d) must be (14, 8), (14, 16), (14, 32), (7, 8), (7, 16) or (7, 32) - the last is
+ * forwarded to ppn_swin_wmsa_fwd's kernels, bit for bit - and shift 0 or w / 2 (7 or 3), else PPN_E_UNSUPPORTED.  NULL pointers,
+ * B / H / W / heads <= 0, heads > 65535, a non-finite or non-positive scale, a dtype other than 0 / 1, any of the four buffers not
+ * 16-byte aligned and a launch of 2^31 work-items or more (B * windows * heads * 256, or * 64 at w = 7) return PPN_E_INVALID; all
+ * of it before any HIP call.  dtype 0 = float32, 1 = bfloat16 (converted on load, float32 softmax and accumulation with the
+ * maximum taken before any exponential, the output rounded once; one VALU kernel form serves both). */
+int ppn_wmsa_fwd(const void* qkv, const void* pad_kv, const float* rpb, void* out, int32_t B, int32_t H, int32_t W, int32_t heads,
+                 int32_t head_dim, int32_t window, int32_t shift, float scale, int32_t dtype, void* stream);
 
 /* Backward of ppn_swin_wmsa_fwd, in its layouts and index arithmetic.  Per (image, window, head), over the 49 slots, with the
  * logit L_ij = scale q_i . k_j + rpb[h][rel(i, j)] + mask_ij (the -100 region mask of a shifted layer, not -inf):

@@ -74,7 +74,7 @@ EXPORTS = ("ppn_version", "ppn_error_string", "ppn_last_hip_error", "ppn_polyfit
            "ppn_gennet_tail_train_workspace", "ppn_gennet_tail_train_fwd", "ppn_gennet_tail_train_bwd", "ppn_gennet_tail_train_tile",
            "ppn_gennet_tail_train_max_blocks",
            "ppn_gennet_s2_tile", "ppn_gennet_s2_max_blocks", "ppn_gennet_s2_wgrad_workspace", "ppn_gennet_s2_down", "ppn_gennet_s2_up",
-           "ppn_gennet_s2_wgrad")
+           "ppn_gennet_s2_wgrad", "ppn_wmsa_fwd")
 
 
 def _load():
@@ -131,6 +131,8 @@ def _load():
                                       C.c_float, C.c_int32, _p]
     lib.ppn_swin_wmsa_fwd.argtypes = [_p, _p, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                       C.c_int32, _p]
+    lib.ppn_wmsa_fwd.argtypes = [_p, _p, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                 C.c_int32, _p]
     lib.ppn_swin_wmsa_bwd.argtypes = [_p, _p, _p, _p, _p, _p, _p, _p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_float, C.c_int32, _p]
     lib.ppn_swin_wmsa_bwd_workspace.argtypes = [C.c_int32] * 4

@@ -403,6 +403,26 @@ int ppn_swin_wmsa_fwd(const void* qkv, const void* pad_kv, const float* rpb, voi
     return PPN_OK;
 }
 
+int ppn_wmsa_fwd(const void* qkv, const void* pad_kv, const float* rpb, void* out, int32_t B, int32_t H, int32_t W, int32_t heads,
+                 int32_t head_dim, int32_t window, int32_t shift, float scale, int32_t dtype, void* stream) {
+    if (!qkv || !pad_kv || !rpb || !out || B <= 0 || H <= 0 || W <= 0 || heads <= 0 || heads > 65535 || (dtype != 0 && dtype != 1))
+        return PPN_E_INVALID;
+    if (!(scale > 0.0f) || scale > 3.0e38f) return PPN_E_INVALID;                        // NaN, inf, zero, negative
+    const bool w14 = window == 14 && (head_dim == 8 || head_dim == 16 || head_dim == 32);   // AESwin's inner stages
+    const bool w7 = window == 7 && (head_dim == 8 || head_dim == 16 || head_dim == 32);     // 32: Swin-B's kernel (swin_wmsa.hip)
+    if ((!w14 && !w7) || (shift != 0 && shift != window / 2)) return PPN_E_UNSUPPORTED;
+    if ((((uintptr_t)qkv | (uintptr_t)pad_kv | (uintptr_t)rpb | (uintptr_t)out) & 15) != 0) return PPN_E_INVALID;   // 16-byte loads / stores
+    // window numbers are 32-bit (token offsets 64-bit); in steps, each within 64 bits: H W < 2^31, so windows per image < 2^31, then
+    // B x that, then x heads x the workgroup's work-items
+    if ((long long)H * W >= 0x7fffffffLL) return PPN_E_INVALID;
+    const long long per_image = (((long long)H + window - 1) / window) * (((long long)W + window - 1) / window);
+    if (per_image >= 0x7fffffffLL || (long long)B * per_image >= 0x7fffffffLL) return PPN_E_INVALID;
+    if ((long long)B * per_image * heads >= 0x7fffffffLL / ppn::wmsa_gen_threads(window)) return PPN_E_INVALID;
+    const int e = ppn::wmsa_gen_launch(qkv, pad_kv, rpb, out, B, H, W, heads, head_dim, window, shift, scale, dtype, (hipStream_t)stream);
+    if (e != 0) return hip_fail((hipError_t)e);
+    return PPN_OK;
+}
+
 int64_t ppn_swin_wmsa_bwd_workspace(int32_t B, int32_t H, int32_t W, int32_t heads) {
     if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || heads > 65535) return -1;
     return ppn::swin_wmsa_bwd_workspace_floats(heads);

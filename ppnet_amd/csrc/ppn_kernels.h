@@ -214,6 +214,11 @@ int mhsa_d8_bwd_launch(const void* qkv, const void* out, const void* dout, void*
                        int dtype, hipStream_t stream);
 int swin_wmsa_launch(const void* qkv, const void* pad_kv, const float* rpb, void* out, int B, int H, int W, int heads, int shift, float scale,
                      int dtype, hipStream_t stream);
+// wmsa_gen.hip: the same forward for window 14 with head dim 8 / 16 / 32 and window 7 with head dim 8 / 16 ((7, 32) is forwarded to
+// swin_wmsa_launch); work-items per workgroup of its kernels (one workgroup per (image, window, head))
+int wmsa_gen_threads(int window);
+int wmsa_gen_launch(const void* qkv, const void* pad_kv, const float* rpb, void* out, int B, int H, int W, int heads, int head_dim, int window,
+                    int shift, float scale, int dtype, hipStream_t stream);
 long long swin_wmsa_bwd_workspace_floats(int heads);
 int swin_wmsa_bwd_launch(const void* qkv, const void* pad_kv, const float* rpb, const void* dout, void* dqkv, float* dpad_kv, float* drpb,
                          float* workspace, int B, int H, int W, int heads, int shift, float scale, int dtype, hipStream_t stream);

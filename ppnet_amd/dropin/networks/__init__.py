@@ -3,7 +3,8 @@ GenNet/networks/__init__.py:1-3 re-exports its sub-modules' names).  With `ppnet
 reference's predict.py builds the HIP-backed AE-ViT: same constructor (`AE(img_channels, out_channels, img_resolution,
 dim)`), same 87 state-dict keys, `load_state_dict(torch.load(p)['model'])` unchanged.  `token2feature` / `feature2token`
 are the two helpers of networks/base.py:43-52 that scripts import by name.  `AESwin` (the commented-out alternative,
-predict.py:12) is out of scope: asking for it raises with that message instead of an ImportError further down."""
+predict.py:12) is not re-exported here: asking the package for it raises with that message instead of an ImportError further
+down.  The model itself is built: import it from its own module, `from networks.ae_swin import AESwin` (ppnet_amd.gennet.AESwin)."""
 from ppnet_amd.gennet import AE, AEViT, normalize_heatmap_u8  # noqa: F401
 
 
@@ -22,7 +23,8 @@ def feature2token(x):
 def __getattr__(name):
     if name == "AESwin":
         raise NotImplementedError("networks.AESwin: the shifted-window variant is not the selected model "
-                                  "(GenNet/predict.py:12 keeps it commented out) and is out of this build's scope")
+                                  "(GenNet/predict.py:12 keeps it commented out) and the package does not re-export it; "
+                                  "import it from its module: from networks.ae_swin import AESwin")
     raise AttributeError(name)
 
 

@@ -7,6 +7,10 @@ Structure: conv3x3+BN+LeakyReLU stem, int(log2(R//28)) stride-2 conv stages, 3 p
 MLP x4, GELU, LN eps 1e-6) on the (R/2^n)^2 tokens, mirrored transposed-conv stages, conv3x3 to out_channels.
 Dense work runs on the ROCm libraries through PyTorch (bf16 autocast optional); pinned against the reference's
 own module by tests/golden/g13_aevit.npz.
+
+AESwin (reference GenNet/networks/ae_swin.py on vanilla_swin.py and base.py), the reference's second model, is below AEViT: five
+Swin stages with 7 x 7 and 14 x 14 windows between the same kind of conv encoder and decoder, GPU inference on the window-attention
+kernels (swin.wmsa_forward); pinned against the reference's own module by tests/golden/g25_aeswin.npz.
 """
 import math
 from functools import partial
@@ -18,7 +22,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import fused
-from .dense import drop_path
+from . import swin
+from .dense import drop_path, gpu_inference, linear
 from .vit import mhsa_autograd
 
 
@@ -220,14 +225,7 @@ class AEViT(nn.Module):
         """After the checkpoint is loaded: fold every eval-mode BatchNorm into the (transposed) convolution in front of
         it (exact algebra in float32) and switch the convolution weights to channels_last. Load the state dict first."""
         for stage in [self.conv_first, *self.enc_conv, *self.dec_conv]:
-            conv, bn = stage[0], stage[1]
-            if not isinstance(bn, nn.BatchNorm2d):
-                continue
-            scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).detach()
-            shape = (1, -1, 1, 1) if isinstance(conv, nn.ConvTranspose2d) else (-1, 1, 1, 1)     # out-channel axis
-            conv.weight = nn.Parameter(conv.weight.detach() * scale.view(shape))
-            conv.bias = nn.Parameter(((conv.bias.detach() if conv.bias is not None else 0) - bn.running_mean) * scale + bn.bias.detach())
-            stage[1] = nn.Identity()
+            _fold_bn(stage)
         self.to(memory_format=torch.channels_last)
         self.conv_first = _FusedStage(self.conv_first[0], self.conv_first[2].negative_slope)
         self.enc_conv = nn.ModuleList(_FusedStage(st[0], st[2].negative_slope) for st in self.enc_conv)
@@ -309,6 +307,203 @@ class AEViT(nn.Module):
             wf, bf = self._final_pack()                                      # dim -> 1 at full resolution: direct HIP kernel
             return fused.conv3x3_to1(x, wf, bf)
         return c(x)
+
+
+class _WindowAttention(nn.Module):
+    """vanilla_swin.py:191-284: parameters relative_position_bias_table [(2w-1)^2, heads], qkv, proj; buffer relative_position_index.
+    forward takes the qkv projection's input on the token GRID [B,H,W,C] (after norm1) — padding, shift, window partition, mask,
+    window reverse, reverse shift and crop (vanilla_swin.py:334-368) are index arithmetic of the kernel / of swin.window_attention."""
+
+    def __init__(self, dim, window, num_heads, shift):
+        super().__init__()
+        self.dim, self.window, self.num_heads, self.shift = dim, window, num_heads, shift
+        self.scale = (dim // num_heads) ** -0.5
+        self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * window - 1) ** 2, num_heads))
+        self.register_buffer("relative_position_index", swin._relative_index(window))
+        self.qkv = nn.Linear(dim, dim * 3)
+        self.proj = nn.Linear(dim, dim)
+        nn.init.trunc_normal_(self.relative_position_bias_table, std=0.02)
+        self._rpb32 = fused.WeightCache()                 # the table as the kernel's float32 [heads, 2w-1, 2w-1]
+
+    def on_kernel(self, qkv):
+        """GPU inference (CUDA, no autograd) in float32 / bfloat16 with a (window, head dim) of the HIP kernels; PPNET_LIBRARY_WMSA=1
+        (read here, at call time) keeps the torch composition."""
+        return (gpu_inference(qkv) and qkv.dtype in (torch.float32, torch.bfloat16) and self.dim % self.num_heads == 0
+                and swin.kernel_takes(self.window, self.dim // self.num_heads) and not os.environ.get("PPNET_LIBRARY_WMSA"))
+
+    def attend(self, qkv):
+        """qkv [B,H,W,3C] -> the attention output [B,H,W,C] before proj: ppn_wmsa_fwd / ppn_swin_wmsa_fwd (swin.wmsa_forward) where
+        on_kernel holds, the differentiable torch composition everywhere else (CPU, autograd, head dims 4 / 2 / 1 of dim = 24)."""
+        t = self.relative_position_bias_table
+        if self.on_kernel(qkv):
+            rpb = self._rpb32.get((t,), lambda: swin.bias_table_hw(t.detach().float(), self.num_heads, self.window).contiguous())
+            return swin.wmsa_forward(qkv, self.qkv.bias, rpb, self.num_heads, self.shift, self.scale, self.window)
+        return swin.window_attention(qkv, self.qkv.bias, t, self.num_heads, self.shift, self.scale, self.window)
+
+    def forward(self, x):
+        B, H, W, C = x.shape
+        x2 = x.reshape(-1, C)
+        fast = gpu_inference(x)
+        qkv = (linear(x2.contiguous(), self.qkv) if fast else self.qkv(x2)).view(B, H, W, 3 * C)
+        o = self.attend(qkv).reshape(-1, C)
+        return (linear(o.contiguous(), self.proj) if fast else self.proj(o)).view(B, H, W, C)
+
+
+class _SwinMlp(nn.Module):
+    """vanilla_swin.py:168-188 with the reference's activation for this model: LeakyReLU, not GELU (vanilla_swin.py:171,306)."""
+
+    def __init__(self, dim, hidden):
+        super().__init__()
+        self.fc1 = nn.Linear(dim, hidden)
+        self.fc2 = nn.Linear(hidden, dim)
+
+    def forward(self, x):
+        if gpu_inference(x):
+            x2 = x.reshape(-1, x.shape[-1]).contiguous()
+            return linear(F.leaky_relu_(linear(x2, self.fc1)), self.fc2).view(x.shape)
+        return self.fc2(F.leaky_relu(self.fc1(x)))
+
+
+class _SwinBlock(nn.Module):
+    """vanilla_swin.py:287-376 on the token grid [B,H,W,C]: x + drop_path(attn(norm1(x))), then x + drop_path(mlp(norm2(x)))."""
+
+    def __init__(self, dim, num_heads, window, shift, drop_path=0.0):
+        super().__init__()
+        self.norm1 = nn.LayerNorm(dim)
+        self.attn = _WindowAttention(dim, window, num_heads, shift)
+        self.norm2 = nn.LayerNorm(dim)
+        self.mlp = _SwinMlp(dim, int(dim * 4))
+        self.drop_path_rate = float(drop_path)
+
+    def forward(self, x, y=None, next_norm=None):
+        """x: the residual stream; y = norm1(x) if the caller has it.  Returns (x', next_norm(x') or None)."""
+        if gpu_inference(x):
+            # LayerNorm and the residual adds on the fused kernels (x is updated in place: the stage hands over a fresh tensor)
+            if y is None:
+                y = fused.layer_norm(x, self.norm1)
+            x, y2 = fused.residual_layer_norm(x, self.attn(y), None, self.norm2)
+            return fused.residual_layer_norm(x, self.mlp(y2), None, next_norm)
+        x = x + drop_path(self.attn(self.norm1(x)), self.drop_path_rate, self.training)
+        x = x + drop_path(self.mlp(self.norm2(x)), self.drop_path_rate, self.training)
+        return x, None
+
+
+class _Resample(nn.Module):
+    """base.py:4-40, PatchMerging / PatchUpsampling: a stride-2 (transposed) convolution + BatchNorm2d + LeakyReLU on the token grid
+    (key `conv.{0,1}`).  [B,H,W,C] -> [B,H',W',C]."""
+
+    def __init__(self, conv):
+        super().__init__()
+        self.conv = _stage(conv)
+
+    def forward(self, x):
+        return _run_stage(self.conv, x.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+
+
+class _SwinStage(nn.Module):
+    """vanilla_swin.py:379-467, BasicLayer: `depth` blocks, the odd ones shifted by window // 2 — always, also when one window covers
+    the whole grid (vanilla_swin.py:406,414) — then the optional resampling."""
+
+    def __init__(self, dim, depth, num_heads, window, drop_path, downsample):
+        super().__init__()
+        self.blocks = nn.ModuleList(_SwinBlock(dim, num_heads, window, 0 if i % 2 == 0 else window // 2, drop_path[i]) for i in range(depth))
+        self.downsample = downsample
+
+    def forward(self, x):
+        if gpu_inference(x):
+            x = x.contiguous().clone()                     # the fused kernels update the stream in place
+        y = None
+        for i, blk in enumerate(self.blocks):
+            x, y = blk(x, y, self.blocks[i + 1].norm1 if i + 1 < len(self.blocks) else None)
+        return x if self.downsample is None else self.downsample(x)
+
+
+class AESwin(nn.Module):
+    """GenNet's second model (reference GenNet/networks/ae_swin.py:10-85 on vanilla_swin.py and base.py) with the reference's constructor
+    and its state-dict keys (`conv_first.{0,1}`, `enc_conv.i.{0,1}`, `swin.s.blocks.j.{norm1,attn.{relative_position_bias_table,
+    relative_position_index,qkv,proj},norm2,mlp.{fc1,fc2}}`, `swin.s.downsample.conv.{0,1}` on stages 0, 1, 3, 4, `dec_conv.i.{0,1}`,
+    `conv_final`), so a reference checkpoint loads with strict=True.
+
+    Structure: conv3x3 + BN + LeakyReLU stem, int(log2(R // 56)) stride-2 conv stages, five Swin stages (depths 2, 3, 4, 3, 2; heads 6,
+    12, 24, 12, 6; windows 7, 14, 14, 14, 7; LeakyReLU MLP x4; LN eps 1e-5; drop path 0.1 spread over the 14 blocks) on token grids
+    g, g/2, g/4, g/4, g/2 with stride-2 (transposed) convolutions between them, mirrored transposed-conv stages, conv3x3 to
+    out_channels.  GPU inference runs the window attention on ppn_wmsa_fwd / ppn_swin_wmsa_fwd, LayerNorm and the residual adds on the
+    fused kernels and the Linears through dense.linear; the LeakyReLU, the dim-channel convolutions and everything under autograd or
+    on the CPU are library ops."""
+
+    DEPTHS, RATIOS, HEADS, WINDOWS = (2, 3, 4, 3, 2), (0.5, 0.5, 1, 2, 2), (6, 12, 24, 12, 6), (7, 14, 14, 14, 7)
+
+    def __init__(self, img_channels, out_channels, img_resolution=256, dim=192):
+        super().__init__()
+        n_down = int(math.log2(img_resolution // 56))                        # ae_swin.py:21
+        self.conv_first = _stage(nn.Conv2d(img_channels, dim, 3, 1, 1))
+        self.enc_conv = nn.ModuleList(_stage(nn.Conv2d(dim, dim, 3, 2, 1)) for _ in range(n_down))
+        dpr = [float(v) for v in torch.linspace(0, 0.1, sum(self.DEPTHS))]   # ae_swin.py:35-36
+        self.swin = nn.ModuleList()
+        for i, depth in enumerate(self.DEPTHS):
+            r = self.RATIOS[i]
+            merge = (_Resample(nn.Conv2d(dim, dim, 3, 2, 1)) if r < 1 else
+                     _Resample(nn.ConvTranspose2d(dim, dim, 3, 2, 1, output_padding=1)) if r > 1 else None)
+            lo = sum(self.DEPTHS[:i])
+            self.swin.append(_SwinStage(dim, depth, self.HEADS[i], self.WINDOWS[i], dpr[lo:lo + depth], merge))
+        self.dec_conv = nn.ModuleList(_stage(nn.ConvTranspose2d(dim, dim, 3, 2, 1, output_padding=1)) for _ in range(n_down))
+        self.conv_final = nn.Conv2d(dim, out_channels, 3, 1, 1)
+        self._final_f32 = None                            # set by prepare_inference(): WeightCache of (float32 weight, float bias)
+
+    def _conv_stages(self):
+        """(owner, attribute or index) of every conv + BatchNorm + LeakyReLU stage, the four inside the Swin stages included."""
+        out = [(self, "conv_first")]
+        out += [(self.enc_conv, i) for i in range(len(self.enc_conv))]
+        out += [(st.downsample, "conv") for st in self.swin if st.downsample is not None]
+        return out + [(self.dec_conv, i) for i in range(len(self.dec_conv))]
+
+    def prepare_inference(self):
+        """As AEViT.prepare_inference: fold every eval-mode BatchNorm into the (transposed) convolution in front of it (float32
+        algebra), switch the convolution weights to channels_last and wrap each stage in _FusedStage.  Load the state dict first."""
+        stages = self._conv_stages()
+        for owner, key in stages:
+            stage = getattr(owner, key) if isinstance(key, str) else owner[key]
+            _fold_bn(stage)
+        self.to(memory_format=torch.channels_last)
+        for owner, key in stages:
+            stage = getattr(owner, key) if isinstance(key, str) else owner[key]
+            f = _FusedStage(stage[0], stage[2].negative_slope)
+            if isinstance(key, str):
+                setattr(owner, key, f)
+            else:
+                owner[key] = f
+        self._final_f32 = fused.WeightCache()
+        return self
+
+    def forward(self, x):
+        x = self.conv_first(x)
+        for blk in self.enc_conv:
+            x = _run_stage(blk, x)
+        x = x.permute(0, 2, 3, 1)                                            # feature2token, kept as a grid: [B,H,W,C]
+        for stage in self.swin:
+            x = stage(x)
+        x = x.permute(0, 3, 1, 2)                                            # token2feature
+        for blk in self.dec_conv:
+            x = _run_stage(blk, x)
+        c = self.conv_final
+        if x.is_cuda and self._final_f32 is not None and c.out_channels == 1 and c.in_channels % 8 == 0 and c.in_channels <= 32:
+            wf, bf = self._final_f32.get((c.weight, c.bias), lambda: (
+                c.weight.detach().float().contiguous(), float(c.bias.detach().float()[0]) if c.bias is not None else 0.0))
+            return fused.conv3x3_to1(x, wf, bf)                              # dim -> 1 at full resolution: direct HIP kernel
+        return c(x)
+
+
+def _fold_bn(stage):
+    """Fold the eval-mode BatchNorm2d of a (conv, BatchNorm2d, LeakyReLU) stage into its (transposed) convolution, exactly, in the
+    parameters' dtype; the BatchNorm becomes an Identity."""
+    conv, bn = stage[0], stage[1]
+    if not isinstance(bn, nn.BatchNorm2d):
+        return
+    scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).detach()
+    shape = (1, -1, 1, 1) if isinstance(conv, nn.ConvTranspose2d) else (-1, 1, 1, 1)             # out-channel axis
+    conv.weight = nn.Parameter(conv.weight.detach() * scale.view(shape))
+    conv.bias = nn.Parameter(((conv.bias.detach() if conv.bias is not None else 0) - bn.running_mean) * scale + bn.bias.detach())
+    stage[1] = nn.Identity()
 
 
 def stem_from_moments(x, dz, w, b, gamma, beta, eps, slope):

@@ -11,6 +11,9 @@ Two forms of the same arithmetic:
   so a block saves qkv, the qkv bias and the bias table and nothing of size 49 x 49; the gradients of qkv, of the qkv bias (the
   padded positions' k / v) and of the bias table are bitwise reproducible.
 * everything else (CPU, other head dims or windows): a pure-torch composition of mmseg's ops (`window_attention`).
+
+`wmsa_forward` also serves GenNet's AESwin (gennet.py): window 14 with head dims 8 / 16 / 32 and window 7 with head dims 8 / 16 run on
+ppn_wmsa_fwd (csrc/wmsa_gen.hip), forward only; the backbone above asks for window 7 / head dim 32 only and is unchanged.
 """
 import ctypes
 
@@ -99,8 +102,18 @@ def _relative_index(window, device=None):
     return (c + c.T).flip(1).contiguous().to(device)
 
 
+# (window, head dim) of ppn_wmsa_fwd (csrc/wmsa_gen.hip): GenNet's AESwin.  (7, 32), Swin-B's shape, stays on ppn_swin_wmsa_fwd.
+GEN_SHAPES = ((14, 8), (14, 16), (14, 32), (7, 8), (7, 16))
+
+
+def kernel_takes(window, head_dim):
+    """Whether a HIP forward kernel exists for this (window, head dim)."""
+    return (window, head_dim) == (WINDOW, HEAD_DIM) or (window, head_dim) in GEN_SHAPES
+
+
 def wmsa_forward(qkv, pad_kv, rpb_hw, heads, shift, scale, window=WINDOW):
-    """ppn_swin_wmsa_fwd: qkv [B,H,W,3C] CUDA (float32 / bfloat16), pad_kv [3C], rpb_hw [heads,13,13] float32 -> [B,H,W,C]."""
+    """qkv [B,H,W,3C] CUDA (float32 / bfloat16), pad_kv [3C], rpb_hw [heads,2w-1,2w-1] float32 -> [B,H,W,C]; the head dim is
+    C / heads.  ppn_swin_wmsa_fwd for window 7 / head dim 32, ppn_wmsa_fwd for GEN_SHAPES."""
     out = _wmsa_launch(qkv, pad_kv, rpb_hw, heads, shift, scale, window)
     CALLS["kernel"] += 1
     return out
@@ -111,7 +124,9 @@ def _wmsa_launch(qkv, pad_kv, rpb_hw, heads, shift, scale, window=WINDOW):
         raise RuntimeError("ppnet_amd.swin: the window-attention kernel runs on the GPU only (no CPU fallback)")
     B, H, W, C3 = qkv.shape
     C = C3 // 3
-    if C != heads * HEAD_DIM:
+    head_dim = C // max(heads, 1)
+    gen = C == heads * head_dim and (window, head_dim) in GEN_SHAPES
+    if C != heads * HEAD_DIM and not gen:
         raise NotImplementedError(f"head dim {C // max(heads, 1)}: the kernel takes head dim {HEAD_DIM}")
     dtype = {torch.float32: 0, torch.bfloat16: 1}.get(qkv.dtype)
     if dtype is None:
@@ -125,11 +140,14 @@ def _wmsa_launch(qkv, pad_kv, rpb_hw, heads, shift, scale, window=WINDOW):
     if TIMING is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
+    ptrs = (ctypes.c_void_p(qkv.data_ptr()), ctypes.c_void_p(pad_kv.data_ptr()), ctypes.c_void_p(rpb_hw.data_ptr()),
+            ctypes.c_void_p(out.data_ptr()))
     with torch.cuda.device(qkv.device):
-        rc = L.lib.ppn_swin_wmsa_fwd(ctypes.c_void_p(qkv.data_ptr()), ctypes.c_void_p(pad_kv.data_ptr()), ctypes.c_void_p(rpb_hw.data_ptr()),
-                                     ctypes.c_void_p(out.data_ptr()), B, H, W, heads, window, shift, float(scale), dtype,
-                                     ctypes.c_void_p(stream.cuda_stream))
-    L.check(rc, "ppn_swin_wmsa_fwd")
+        if gen:
+            rc = L.lib.ppn_wmsa_fwd(*ptrs, B, H, W, heads, head_dim, window, shift, float(scale), dtype, ctypes.c_void_p(stream.cuda_stream))
+        else:
+            rc = L.lib.ppn_swin_wmsa_fwd(*ptrs, B, H, W, heads, window, shift, float(scale), dtype, ctypes.c_void_p(stream.cuda_stream))
+    L.check(rc, "ppn_wmsa_fwd" if gen else "ppn_swin_wmsa_fwd")
     if ev is not None:
         ev[1].record()
         TIMING.append((ev[0], ev[1], B * H * W, C, qkv.element_size()))

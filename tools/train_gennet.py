@@ -60,6 +60,8 @@ def evaluate(torch, model, dev, R, args, seed=987654321):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--R", type=int, default=256)
+    ap.add_argument("--arch", choices=("aevit", "aeswin"), default="aevit", help="GenNet/networks: AEViT (the selected model) or AESwin")
+    ap.add_argument("--dim", type=int, default=None, help="channel width (default: 24 for aevit, as shipped; 192 for aeswin, ae_swin.py:11)")
     ap.add_argument("--steps", type=int, default=6000)
     ap.add_argument("--paths", type=int, default=8, help="target paths per step")
     ap.add_argument("--placements", type=int, default=8, help="placements per target path (batch = paths x placements)")
@@ -75,15 +77,18 @@ def main():
     args = ap.parse_args()
 
     from ppnet_amd import edage, train
-    from ppnet_amd.gennet import AEViT
+    from ppnet_amd.gennet import AESwin, AEViT
     dev = torch.device("cuda:0")
     torch.manual_seed(args.seed)
     R = args.R
-    model = AEViT(1, 1, R, 24).to(dev)
+    if args.arch == "aeswin":
+        model = AESwin(1, 1, R, args.dim or 192).to(dev)
+    else:
+        model = AEViT(1, 1, R, args.dim or 24).to(dev)
     opt = train.gennet_optimizer(model, args.lr)
     sched = train.PolyLR(opt, args.steps, power=0.9)
     batch = args.paths * args.placements
-    log = {"R": R, "steps": args.steps, "batch": batch, "lr": args.lr, "amp": bool(args.amp), "params": sum(p.numel() for p in model.parameters()),
+    log = {"arch": args.arch, "R": R, "steps": args.steps, "batch": batch, "lr": args.lr, "amp": bool(args.amp), "params": sum(p.numel() for p in model.parameters()),
            "history": []}
     t0 = time.time()
     loss_acc, n_acc = 0.0, 0
